@@ -12,6 +12,22 @@ configs[1]) on synthetic 16 kHz audio, hot path end to end on the GPU:
 Prints ONE JSON line on rank 0.  A "step" is one optimizer step on one batch of
 B utterances per GPU; `value` = audio frames (10 ms) processed per second by the
 whole job, inputs resident in HBM when the timed region starts.
+
+A plain run measures only that: set-up, warm-up (with the eager / graph-replay
+calibration that picks the timed launch mode), the timed steps, the line.  `--full`
+adds the rest: the live roofline of the GEMM class (event-bracketed eager steps),
+the other arithmetic modes, the CPU baselines and the attention-rescoring decode
+RTF; each of those keeps its `--no-*` switch.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy
+files: its `loss` (the line's) and `acc`, and a fixed seeded sample of the parameter
+arena after its update (`params_sample`) and of its gradient arena (`grads_sample`).
+With the option the last timed step starts from the training state saved before the
+first step (weights, Adam moments and step count, dropout counters), put back on the
+stream in front of it (the copies' time is not counted): the state that the chained
+steps reach is not the same from run to run (split-K GEMMs accumulate with float
+atomics, and Adam carries those rounding differences from step to step), so the
+inputs of the dumped step would not be either.
 """
 import argparse
 import json
@@ -47,6 +63,7 @@ DTYPE_NAMES = {0: "f32", 1: "bf16 (MFMA inputs; fp32 storage, accumulate, softma
                   "dropped terms < 2^-24 |a||b| - tests hold it to the exact-fp32 mode's tolerances)",
                3: "bf16x3 (matrix products as hi*hi+hi*lo+lo*hi on bf16 MFMA: ~2^-17 relative error per product, fp32 accumulate - "
                   "narrower than the reference's fp32 products, wider than bf16; fp32 storage and fp32 everywhere else)"}
+DUMP_SAMPLE = 1 << 22          # entries of each arena written by --dump-outputs (16 MB each in float32)
 
 
 def synth_batch(B, seconds, L, seed, device):
@@ -209,14 +226,24 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-decode-utts", type=int, default=16, help="utterances of the decode workload the CPU baseline rescoring times (the first warms up)")
     ap.add_argument("--no-other-modes", action="store_true", help="skip the extra ms/step measurements in arithmetic modes 0 (fp32) and 1 (bf16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the GEMM roofline, the other arithmetic modes, the CPU baselines and the "
+                         "decode RTF (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="start the last timed step from the seeded training state and write what it computed to DIR/<name>.npy "
+                         "(float32, a seeded sample of the arenas)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.gemm_table and not args.full:
+        ap.error("--gemm-table is part of the roofline measurement: add --full")
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a version banner at its first collective):
     # keep the real stdout for the line alone and send everything else that reaches descriptor 1 to stderr.
     sys.stdout.flush()
     real_stdout = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
 
-    from openeat_amd import ddp, hip
+    from openeat_amd import ddp, hip, ops
     hip.GEMM_PRECISION = int(os.environ.get("OE_GEMM_PRECISION", "6"))      # default: the reference-precision 6-term bf16 split
     rank, local, world = ddp.init_from_env()
     assert world == args.gpus or (world == 1 and args.gpus == 1), f"--gpus {args.gpus} but WORLD_SIZE={world}"
@@ -263,6 +290,7 @@ def main():
 
     engine.model = WithFrontend(model)
     batch = {"wav": wav, "targets": tgt, "targets_length": tlen}
+    seeded = [t.clone() for t in train_state(engine)] if args.dump_outputs else None
     # Step launch mode: both are tried during warm-up and the faster one is timed (the decision is the same on every
     # rank: MAX over ranks of each timing).  Graph replay has no host work; the eager step is host-bound on some boxes
     # but overlaps more: at N = 1 the side-stream weight gradients, at N > 1 the gradient all-reduce, which the autograd
@@ -370,11 +398,16 @@ def main():
         torch.cuda.synchronize()
 
     barrier()
+    restore = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if seeded is not None and i == args.steps - 1:
+            restore = restore_seeded(engine, seeded, ops)
         out = run()
     barrier()
     elapsed = time.perf_counter() - t0
+    if restore is not None:                             # the restore's copies ran on the stream between two steps: not a step's time
+        elapsed -= restore[0].elapsed_time(restore[1]) * 1e-3
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -383,6 +416,81 @@ def main():
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.batch * T / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:                 # before anything below moves the weights again
+        dump_outputs(args.dump_outputs, out, engine.arena)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    roof, other, cpu, dec = None, {}, None, None
+    if args.full:
+        roof, other, cpu, dec = full_measurements(args, rank, world, T, dev, engine, batch, fb)
+
+    if rank == 0:
+        line = {"metric": METRIC, "value": value, "unit": "audio-frames/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": DTYPE_NAMES[hip.GEMM_PRECISION], "data": "synthetic",
+                "config": {"workload": "configs[1]: 12L Conformer d=256 (12+3+3, h=4, ff=1024, K=15, V=3246), "
+                                       f"B={args.batch}/GPU x {args.seconds:g} s 16 kHz wav (T={T} frames), L={args.target_len}, "
+                                       "CTC+attention joint loss, fbank+fwd+bwd+clip+Adam, dropout 0.1",
+                           "global_batch": world * args.batch, "parallelism": f"dp{world}", "hip_graph": use_graph,
+                           **({"graph_form": graph_form} if use_graph and engine.reducer.active else {}),
+                           **({"ddp_forced_with_one_rank": "OE_DDP_FORCE=1: RCCL process group, hooks and all-reduces (over a group of one) "
+                                                           "inside the timed step"} if ddp.forced() else {})},
+                **({"invalid": f"dropout overridden to {args.dropout}"} if args.dropout is not None else {}),
+                "loss": loss, "roofline": roof, "cpu_baseline": cpu, **other, "decode": dec}
+        real_stdout.write(json.dumps(line) + "\n")
+        real_stdout.flush()
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
+def train_state(engine):
+    """The device tensors a training step reads and moves on: weights, Adam moments and step count, dropout step counter."""
+    o = engine.optimizer
+    return [engine.arena.flat, o.exp_avg, o.exp_avg_sq, o.step_state, engine.seed_counter]
+
+
+def restore_seeded(engine, seeded, ops):
+    """Put the training state saved before the first step back (--dump-outputs, in front of the last timed step), so that the
+    step whose results are dumped starts from the same weights, Adam state and dropout counters in every run.  Dropout masks:
+    a replayed graph mixes the seeds drawn at capture time with the device step counter restored here; an eager step draws
+    host seeds at every dropout site, reset here to where the first step drew them (no site draws before it).  -> the event
+    pair around the copies (their time is taken out of the timed region)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for t, s in zip(train_state(engine), seeded):
+        t.copy_(s)
+    e1.record()
+    engine.arena.mark_step()
+    ops.manual_seed(0)
+    return e0, e1
+
+
+def dump_outputs(path, out, arena):
+    """A step's results as DIR/<name>.npy: its loss and accuracy, and the same seeded sample of entries of the
+    parameter arena (after the update) and of the gradient arena (the step's gradients); the whole arena if it is smaller.
+    The sample is one seeded random entry out of each of DUMP_SAMPLE equal blocks of the arena."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = arena.flat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        stride = n // DUMP_SAMPLE
+        idx = torch.arange(DUMP_SAMPLE) * stride + torch.randint(stride, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+    arrays = {"loss": out[0], "acc": out[1], "params_sample": arena.flat.detach(), "grads_sample": arena.grad.detach()}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.reshape(-1).cpu()
+        if name.endswith("_sample") and idx is not None:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().numpy())
+
+
+def full_measurements(args, rank, world, T, dev, engine, batch, fb):
+    """--full: what the headline figure does not need -> (roofline, other arithmetic modes, CPU baseline, decode)."""
+    from openeat_amd import hip
+    from openeat_amd.frontend import utt_normalize_
+    from openeat_amd.models.asr_model import ASRModel
 
     # ---- roofline of the dominant kernel (fp32 MFMA GEMM), measured live with HIP events on the launch stream
     roof = None
@@ -509,24 +617,7 @@ def main():
         del dec_model, lm
         engine.arena.enabled = True
         log(f"decode done: RTF {dec['rtf']:.5f} ({dec['wall_s'] * 1e3:.0f} ms for {dec['utterances']} x {args.seconds:g} s)")
-
-    if rank == 0:
-        line = {"metric": METRIC, "value": value, "unit": "audio-frames/s", "n_gpus": world, "steps": args.steps,
-                "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": DTYPE_NAMES[hip.GEMM_PRECISION], "data": "synthetic",
-                "config": {"workload": "configs[1]: 12L Conformer d=256 (12+3+3, h=4, ff=1024, K=15, V=3246), "
-                                       f"B={args.batch}/GPU x {args.seconds:g} s 16 kHz wav (T={T} frames), L={args.target_len}, "
-                                       "CTC+attention joint loss, fbank+fwd+bwd+clip+Adam, dropout 0.1",
-                           "global_batch": world * args.batch, "parallelism": f"dp{world}", "hip_graph": use_graph,
-                           **({"graph_form": graph_form} if use_graph and engine.reducer.active else {}),
-                           **({"ddp_forced_with_one_rank": "OE_DDP_FORCE=1: RCCL process group, hooks and all-reduces (over a group of one) "
-                                                           "inside the timed step"} if ddp.forced() else {})},
-                **({"invalid": f"dropout overridden to {args.dropout}"} if args.dropout is not None else {}),
-                "loss": loss, "roofline": roof, "cpu_baseline": cpu, **other, "decode": dec}
-        real_stdout.write(json.dumps(line) + "\n")
-        real_stdout.flush()
-    if torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
+    return roof, other, cpu, dec
 
 
 if __name__ == "__main__":

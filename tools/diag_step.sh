@@ -3,7 +3,7 @@
 set -o pipefail
 OUT=gpurun_out/diag; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-decode --no-other-modes --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-decode --no-other-modes --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench.json'));print('ms_per_step', d['ms_per_step'], 'gemm', d['roofline']['gemm_ms_per_step'], 'loss', d['loss'])"
 if [ "${1:-}" = "trace" ]; then
 rm -rf $OUT/tg

@@ -1,10 +1,10 @@
 #!/bin/bash
 # GPU box: where the GEMM kernels' wave cycles go inside the training step - two rocprofv3 --pmc passes (--kernel-trace only) of
-# `bench.py --no-graph --single-stream`: SQ wait / issue / MFMA / LDS counters, then L2 hit / miss counters; per-kernel averages.
+# `bench.py --full --no-graph --single-stream`: SQ wait / issue / MFMA / LDS counters, then L2 hit / miss counters; per-kernel averages.
 set -o pipefail
 OUT=gpurun_out/gemm_pmc; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-CMD="python3 bench.py --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps 2 --warmup 1 ${BENCH_ARGS:-}"     # BENCH_ARGS: e.g. the north-star shape
+CMD="python3 bench.py --full --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps 2 --warmup 1 ${BENCH_ARGS:-}"     # BENCH_ARGS: e.g. the north-star shape
 rm -rf $OUT/sq $OUT/sq2 $OUT/tcc
 timeout -k 10 500 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT/sq -o sq --output-format csv -- $CMD > $OUT/sq.log 2>&1 || { tail -5 $OUT/sq.log; exit 1; }
 timeout -k 10 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES SQ_ACTIVE_INST_VALU --kernel-trace -d $OUT/sq2 -o sq2 --output-format csv -- $CMD > $OUT/sq2.log 2>&1 || { tail -5 $OUT/sq2.log; echo "(second SQ pass failed: counter names?)"; }

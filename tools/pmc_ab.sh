@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for V in $A $B; do
   export $VAR=$V
   rm -rf $OUT/p_$V
-  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/p_$V -o p --output-format csv -- python3 bench.py --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps 2 --warmup 1 > $OUT/log_$V.txt 2>&1 || { tail -5 $OUT/log_$V.txt; exit 1; }
+  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/p_$V -o p --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps 2 --warmup 1 > $OUT/log_$V.txt 2>&1 || { tail -5 $OUT/log_$V.txt; exit 1; }
   python - "$OUT/p_$V/p_counter_collection.csv" "$PAT" "$VAR=$V" <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))

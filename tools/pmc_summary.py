@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; each with --kernel-trace only) of
-`bench.py --no-graph` into profiles/<tag>_pmc_hbm_traffic.json + a per-kernel markdown table.
+`bench.py --full --no-graph` into profiles/<tag>_pmc_hbm_traffic.json + a per-kernel markdown table.
 
 Corrections as MI355X_MICROARCH.md prescribes: counter values are KB; on gfx950 FETCH_SIZE reports half of the
 bytes of wide coalesced reads, so it is doubled.
@@ -45,7 +45,7 @@ gl = sum(r[1] for r in g)
 gb = sum(r[2] + r[3] for r in g)
 out = {
     "round": int(tag[1:]), "precision": prec, "steps_in_trace": steps,
-    "command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace --output-format csv -- python3 bench.py --no-graph "
+    "command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace --output-format csv -- python3 bench.py --full --no-graph "
                "--no-cpu-baseline --no-decode (two separate passes)",
     "correction": "KB -> bytes x1024; FETCH_SIZE x2 (gfx950 half-count of wide coalesced reads, MI355X_MICROARCH.md HBM section)",
     "gemm": {"kernels": sorted({r[0] for r in g}), "launches_per_step": gl, "read_bytes_per_step": sum(r[2] for r in g),

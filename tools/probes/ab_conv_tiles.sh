@@ -1,4 +1,4 @@
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-decode --no-other-modes --gemm-table"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-decode --no-other-modes --gemm-table"
 for e in "OE_PL_HYBRID=0" "OE_PL_HYBRID=1"; do
   echo "== $e"; env $e $B 2>&1 >/dev/null | grep -E "\((15[0-9]{4}|256, 2304), " | cut -c1-120
 done

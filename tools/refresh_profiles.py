@@ -43,7 +43,7 @@ line = json.load(open(f"{src}/{tag}_bench_p{P}.json"))
 ro = line["roofline"]
 with open(f"{dst}/{tag}_kernel_stats_p{P}.md", "w") as f:
     f.write(f"# Round {int(tag[1:])} - rocprofv3 kernel stats, bench config 2, precision {P} (final kernels of the round)\n\n")
-    f.write("`rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-decode --no-graph --single-stream --steps 5 --warmup 2` "
+    f.write("`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-decode --no-graph --single-stream --steps 5 --warmup 2` "
             f"({steps:g} optimizer steps in the trace, counted by the Adam kernel's launches: first step + warm-up + timed + 2 event-bracketed; the `spin_kernel` launches that park the "
             f"GPU during the event-bracketed steps are left out).  Full table: `{tag}_kernel_stats_p{P}.csv`.\n\n")
     f.write(f"All kernels: {tot / 1e6 / steps:.2f} ms/step (serialised by the profiler; the un-profiled step is {line['ms_per_step']:.1f} ms).  "

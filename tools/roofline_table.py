@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel-class roofline table for config 2 from the rocprofv3 kernel stats of
-`bench.py --no-graph --single-stream` (profiles/<tag>_kernel_stats_p3.csv): algorithmic work per optimizer step (SURVEY 8d /
+`bench.py --full --no-graph --single-stream` (profiles/<tag>_kernel_stats_p3.csv): algorithmic work per optimizer step (SURVEY 8d /
 DESIGN section 4 formulas) / measured kernel time per step, against the MI355X peaks (8 TB/s HBM, 2.5 PFLOP/s dense bf16).
 
 usage: roofline_table.py <kernel_stats.csv> <steps in trace> > profiles/<tag>_roofline_by_class.md"""
@@ -61,7 +61,7 @@ peak = {"hbm": 8.0e12, "mfma": 2.5e15 / TERMS}      # algorithmic flops: the den
 unit = {"hbm": ("TB/s", 1e12), "mfma": ("TFLOP/s", 1e12)}
 tot = sum(int(r["TotalDurationNs"]) for r in rows if "spin_kernel" not in r["Name"]) / 1e6 / steps
 print(f"# Roofline by kernel class, config 2 (B=32 x 10 s), precision {PREC}\n")
-print("Kernel time: rocprofv3 `--kernel-trace --stats` of `bench.py --no-graph --single-stream` (every kernel alone on one stream), "
+print("Kernel time: rocprofv3 `--kernel-trace --stats` of `bench.py --full --no-graph --single-stream` (every kernel alone on one stream), "
       f"per optimizer step; all kernels {tot:.2f} ms/step.  Work: algorithmic bytes / flops (DESIGN section 4).  Peaks: HBM 8 TB/s, "
       f"dense bf16 MFMA 2.5 PFLOP/s / {TERMS} = {2500 / TERMS:.0f} TFLOP/s of algorithmic flops (precision {PREC} issues {TERMS} MFMAs per product; "
       "the attention class's short-axis (decoder) kernels run on the fp32-input MFMA in this mode and are priced against the same figure).\n")

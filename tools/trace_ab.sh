@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for V in $A $B; do
   export $VAR=$V
   rm -rf $OUT/t_$V
-  timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT/t_$V -o t --output-format csv -- python3 bench.py --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps $STEPS --warmup 2 > $OUT/log_$V.txt 2>&1 || { tail -5 $OUT/log_$V.txt; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT/t_$V -o t --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-decode --no-other-modes --no-graph --single-stream --steps $STEPS --warmup 2 > $OUT/log_$V.txt 2>&1 || { tail -5 $OUT/log_$V.txt; exit 1; }
   python tools/summarize_kernel_trace.py $(ls $OUT/t_$V/*kernel_trace.csv | head -1) $STEPS > $OUT/summary_${VAR}_$V.txt
   rm -rf $OUT/t_$V
   timeout -k 10 300 python bench.py --no-cpu-baseline --no-decode --no-other-modes --steps 20 --warmup 3 > $OUT/bench_${VAR}_$V.json 2>/dev/null || exit 1
