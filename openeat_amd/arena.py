@@ -114,6 +114,10 @@ class ParamArena:
                 g = self.grad[o:o + p.numel()].view(p.shape)
                 p.grad = g
                 self.by_ptr[view.data_ptr()] = g
+        # the parameters moved: packed copies registered at their old addresses (a precision-6 pass before the arena existed)
+        # name freed storage now - neutralise those rows before any refresh launch can read them
+        from . import ops as _ops
+        _ops.pack_tables_sweep()
 
     def activate(self):
         global _ACTIVE

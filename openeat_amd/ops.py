@@ -200,6 +200,13 @@ class _PackTable:
 _ROW = _PackTable(6)        # rows: { W, packed, R, Cc, row stride, transposed }; key = (address, R, Cc, row stride, transposed)
 
 
+def _row_dead(key, ent):
+    """A _ROW row must not be refreshed again: its owner is gone, OR the owner lives on at another address (`p.data = view`:
+    ParamArena, load_state_dict-style re-pointing) - the row's source address is then the freed old storage."""
+    o = ent["owner"]()
+    return o is None or o.data_ptr() + ent.get("off", 0) != key[0]
+
+
 def _pack_done(tab):
     """The refresh launch sits on the current stream: remember it, consumers on OTHER streams (the right-to-left decoder, the CTC
     head) order themselves behind it."""
@@ -211,6 +218,13 @@ def _pack_done(tab):
 def _pack_wait(tab):
     if tab.event is not None and tab.stream != torch.cuda.current_stream():
         torch.cuda.current_stream().wait_event(tab.event)
+
+
+def pack_events_forget():
+    """planes.capture_scope() on exit: an event recorded INSIDE a capture must not be waited on by an eager consumer (every entry
+    is stale after the scope - the generation moves - so the next eager reader refreshes and records a real event)."""
+    for tab in (_ROW, _FFN):
+        tab.event = tab.stream = None
 
 
 def row_packs_clear():
@@ -233,7 +247,7 @@ def _row_packed(w, transposed):
     key = (w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), int(transposed))
     ent = _ROW.entries.get(key)
     capturing = torch.cuda.is_current_stream_capturing()
-    if ent is not None and ent["owner"]() is not owner:       # the address has a new tenant: the old row dies, a new one is appended
+    if ent is not None and (ent["owner"]() is not owner or _row_dead(key, ent)):   # a new tenant: the old row dies, a new one is appended
         if capturing:
             return None
         _ROW.drop(key)
@@ -241,13 +255,13 @@ def _row_packed(w, transposed):
     if ent is None:
         if capturing:
             return None                                       # (its buffer would live in the graph's pool: stay on oe_gemm_f32)
-        ent = dict(owner=weakref.ref(owner), buf=torch.empty(w.shape[0] * w.shape[1] * 6, dtype=torch.uint8, device=w.device), gen=-1, ver=None)
+        ent = dict(owner=weakref.ref(owner), off=key[0] - owner.data_ptr(), buf=torch.empty(w.shape[0] * w.shape[1] * 6, dtype=torch.uint8, device=w.device), gen=-1, ver=None)
         if not _ROW.add(key, [key[0], ent["buf"].data_ptr(), key[1], key[2], key[3], key[4]], ent, w.device):
             return None
     gen, ver = _planes.weights_generation(), owner._version
     if ent["gen"] != gen or ent["ver"] != ver:
         if not capturing:
-            _ROW.sweep(lambda k, e: e["owner"]() is None)
+            _ROW.sweep(_row_dead)
             _ROW.upload()
         elif _ROW.dirty:
             return None
@@ -1361,6 +1375,14 @@ def _ffn_fused_ok(x2, w1, w2, act, res2):
 
 _FFN = _PackTable(9)        # rows: { W1, W2, w1p, w2p, w2tp, w1tp, d, ff, planes }; key = (W1 address, W2 address, precision)
 FFN_PACK_TABLE = os.environ.get("OE_FFN_PACK_TABLE", "1") == "1"
+FFN_FWD_FUSED_LAUNCHES = 0  # (tests: the fused forward / input gradient ran, on packed weights)
+FFN_BWD_FUSED_LAUNCHES = 0
+
+
+def _ffn_dead(key, ent):
+    """A _FFN row must not be refreshed again: W1 or W2 is gone, or lives on at another address (see _row_dead)."""
+    w1, w2 = ent["w1"](), ent["w2"]()
+    return w1 is None or w2 is None or w1.data_ptr() != key[0] or w2.data_ptr() != key[1]
 
 
 def ffn_packs_clear():
@@ -1372,9 +1394,9 @@ def pack_tables_sweep():
     """Neutralise the table rows of weights that have died since the last look (planes.new_pass, TrainEngine.replay: before anything
     - a captured pack launch included - can touch them: their memory may be unmapped by now, torch.cuda.empty_cache)."""
     if torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-        _FFN.sweep(lambda k, e: e["w1"]() is None or e["w2"]() is None)
+        _FFN.sweep(_ffn_dead)
         _FFN.upload()
-        _ROW.sweep(lambda k, e: e["owner"]() is None)
+        _ROW.sweep(_row_dead)
         _ROW.upload()
 
 
@@ -1385,7 +1407,7 @@ def _ffn_packed(w1, w2, d, ff, bwd=False):
     capturing = torch.cuda.is_current_stream_capturing()
     key = (w1.data_ptr(), w2.data_ptr(), prec)
     ent = _FFN.entries.get(key) if FFN_PACK_TABLE else None
-    if ent is not None and ((ent["d"], ent["ff"]) != (d, ff) or ent["w1"]() is not w1 or ent["w2"]() is not w2):
+    if ent is not None and ((ent["d"], ent["ff"]) != (d, ff) or ent["w1"]() is not w1 or ent["w2"]() is not w2 or _ffn_dead(key, ent)):
         if capturing:
             ent = False                                          # (no table surgery inside a capture: a pack of this call's own)
         else:
@@ -1407,7 +1429,7 @@ def _ffn_packed(w1, w2, d, ff, bwd=False):
     gen, ver, kind = _planes.weights_generation(), (w1._version, w2._version), int(bwd)
     if ent["gen"][kind] != gen or ent["ver"][kind] != ver:
         if not capturing:
-            _FFN.sweep(lambda k, e: e["w1"]() is None or e["w2"]() is None)
+            _FFN.sweep(_ffn_dead)
             _FFN.upload()
         if not _FFN.dirty and len(_FFN.entries) > 1 and ent["gen"][0] != gen and ent["gen"][1] != gen:
             # nobody has refreshed anything in this generation yet: all feed-forwards, both orientations, one launch
@@ -1419,7 +1441,9 @@ def _ffn_packed(w1, w2, d, ff, bwd=False):
                 v = (w1e._version, w2e._version) if (w1e is not None and w2e is not None) else None
                 e["gen"], e["ver"] = [gen, gen], [v, v]
         else:
+            _pack_wait(_FFN)                 # behind the last table launch: the event recorded below then covers every entry
             hip.call("oe_ffn_pack_weights_bwd" if bwd else "oe_ffn_pack_weights", w1, w2, d, ff, prec, ent["bufs"][2 * kind], ent["bufs"][2 * kind + 1])
+            _pack_done(_FFN)
             ent["gen"][kind], ent["ver"][kind] = gen, ver
     else:
         _pack_wait(_FFN)
@@ -1463,8 +1487,9 @@ class FeedForwardFn(torch.autograd.Function):
             hip.ffn_fwd(x2, w1p, b1, w2p, b2, M, d, ff, act, drop_in=p_in, seed_in=s_in, drop_out=p_out, seed_out=s_out,
                         seed_dev=_seed_dev, pre_out=pre, act_out=a, residual=res2, ldr=0 if res2 is None else res2.stride(0),
                         beta=out_scale, y=y, lnf=lnf)
+            global LN_FWD_FUSED_LAUNCHES, FFN_FWD_FUSED_LAUNCHES
+            FFN_FWD_FUSED_LAUNCHES += 1
             if lnf is not None:
-                global LN_FWD_FUSED_LAUNCHES
                 lnf_p["done"] = True
                 LN_FWD_FUSED_LAUNCHES += 1
             ctx.save_for_backward(x2, w1, w2, pre, a)
@@ -1517,8 +1542,9 @@ class FeedForwardFn(torch.autograd.Function):
                     _resolve_ln(pend)
             # FIRST launch of this backward: it makes g2 when that is a parked LayerNorm backward (the weight gradient reads it after)
             hip.ffn_bwd(g2, w2tp, w1tp, M, d, ff, act, drop_in=p_in, seed_in=s_in, seed_dev=_seed_dev, pre=pre, dh=dh, dx=dx, ln=ln)
+            global LN_BWD_FUSED_LAUNCHES, FFN_BWD_FUSED_LAUNCHES
+            FFN_BWD_FUSED_LAUNCHES += 1
             if ln is not None:
-                global LN_BWD_FUSED_LAUNCHES
                 pend["done"] = True
                 LN_BWD_FUSED_LAUNCHES += 1
                 _ln_reduce(pend)

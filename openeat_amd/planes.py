@@ -171,6 +171,8 @@ def capture_scope():
         bump_generation()                # whatever the capture "refreshed" (weight planes, packed feed-forward weights) was only
         if a is not None:                # recorded: the next eager reader refreshes for real
             a.mark_step()
+        from . import ops as _ops
+        _ops.pack_events_forget()        # (an event recorded inside the capture is no eager consumer's to wait on)
 
 
 _GEN = 0

@@ -474,3 +474,265 @@ def test_ln_backward_epilogue_is_stable_over_many_launches():
             assert epi["done"]
             worst = max(worst, float((dx1 - dx0).abs().max()))
     assert worst <= 3e-6 * float(dx0.abs().max()) + 1e-6, worst
+
+
+# --------------------------------------------------------------------------------------------------------------------------- #
+# The packed-weight tables (ops._ROW for these kernels, ops._FFN for the fused feed-forward) against the weights' CURRENT values
+# after every way the weights can change: through torch, behind torch's back, by re-pointing a live Parameter's storage, by a
+# new Parameter on a dead one's address, and under a captured graph.  Each check asserts through the launch counters that the
+# packed path ran, compares with a float64 restatement, and checks the tables' host invariant (tests/packcheck.py) BEFORE the
+# launch that follows the mutation can refresh them.
+# --------------------------------------------------------------------------------------------------------------------------- #
+import gc  # noqa: E402
+
+from packcheck import assert_pack_rows_live  # noqa: E402
+
+
+class _Gemm(torch.nn.Module):
+    """One Linear weight through ops.gemm_nt (x W^T) or ops.gemm_nn (dy W) at the shapes of the row-block / tile forms."""
+
+    def __init__(self, kind, rows, n, k, seed):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.kind, self.rows = kind, rows
+        self.w = torch.nn.Parameter((torch.randn(n, k, generator=g) / math.sqrt(k)).to(DEV))
+        self.inp = torch.randn(rows, k if kind == "nt" else n, generator=g).to(DEV)
+
+    def check(self):
+        n0 = ops.ROWGEMM_LAUNCHES
+        with torch.no_grad():
+            got = ops.gemm_nt(self.inp, self.w) if self.kind == "nt" else ops.gemm_nn(self.inp, self.w)
+        assert ops.ROWGEMM_LAUNCHES == n0 + 1, "the packed kernel did not take the call"
+        torch.cuda.synchronize()
+        w, x = self.w.detach().cpu().double(), self.inp.cpu().double()
+        want = x @ w.t() if self.kind == "nt" else x @ w
+        torch.testing.assert_close(got.cpu().double(), want, rtol=1e-4, atol=5e-5)
+
+
+class _Ffn(torch.nn.Module):
+    """ops.feed_forward (swish, scaled residual: the macaron half-step) on the fused forward and the fused input gradient."""
+
+    def __init__(self, d, ff, rows, seed):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.w1 = torch.nn.Parameter((torch.randn(ff, d, generator=g) / math.sqrt(d)).to(DEV))
+        self.b1 = torch.nn.Parameter((torch.randn(ff, generator=g) * 0.1).to(DEV))
+        self.w2 = torch.nn.Parameter((torch.randn(d, ff, generator=g) / math.sqrt(ff)).to(DEV))
+        self.b2 = torch.nn.Parameter((torch.randn(d, generator=g) * 0.1).to(DEV))
+        self.x0 = torch.randn(rows, d, generator=g).to(DEV)
+        self.wgt = torch.randn(rows, d, generator=g).to(DEV)
+
+    def params(self):
+        return [self.w1, self.b1, self.w2, self.b2]
+
+    def run(self):
+        """Forward + backward on the device: (y, dx, dw1, db1, dw2, db2); the grads are zeroed first (arena or not)."""
+        from openeat_amd import arena as A
+        a = A.active()
+        if a is not None:
+            a.zero_grad()
+        else:
+            for p in self.params():
+                p.grad = None
+        x = self.x0.clone().requires_grad_()
+        f0, b0 = ops.FFN_FWD_FUSED_LAUNCHES, ops.FFN_BWD_FUSED_LAUNCHES
+        y = ops.feed_forward(x, self.w1, self.b1, self.w2, self.b2, ops.ACT_SWISH, residual=x, out_scale=0.5)
+        (y * self.wgt).sum().backward()
+        ops.join_side_stream()
+        assert (ops.FFN_FWD_FUSED_LAUNCHES, ops.FFN_BWD_FUSED_LAUNCHES) == (f0 + 1, b0 + 1), "the fused kernels did not take the call"
+        return [y.detach(), x.grad] + [p.grad for p in self.params()]
+
+    def want(self):
+        w1, b1, w2, b2 = (p.detach().cpu().double().requires_grad_() for p in self.params())
+        x = self.x0.cpu().double().requires_grad_()
+        h = x @ w1.t() + b1
+        y = x + 0.5 * ((h * torch.sigmoid(h)) @ w2.t() + b2)
+        (y * self.wgt.cpu().double()).sum().backward()
+        return [y.detach(), x.grad, w1.grad, b1.grad, w2.grad, b2.grad]
+
+    def compare(self, got):
+        torch.cuda.synchronize()
+        want = self.want()
+        torch.testing.assert_close(got[0].cpu().double(), want[0], rtol=1e-4, atol=5e-5)
+        for name, g, w in zip(("dx", "dw1", "db1", "dw2", "db2"), got[1:], want[1:]):
+            torch.testing.assert_close(g.cpu().double(), w, rtol=1e-4, atol=5e-5 * max(1.0, float(w.abs().max())),
+                                       msg=lambda m, name=name: f"{name}: {m}")
+
+    def check(self):
+        self.compare(self.run())
+
+
+_PACK_CASES = {
+    "nt-rowblock-k256": lambda s: _Gemm("nt", 4096, 768, 256, s),     # fused q / k / v projection
+    "nt-rowblock-k512": lambda s: _Gemm("nt", 4133, 128, 512, s),
+    "nn-rowblock-k256": lambda s: _Gemm("nn", 4096, 256, 512, s),     # input gradient: reduction over 256, 512 wide
+    "nt-tile": lambda s: _Gemm("nt", 992, 256, 256, s),
+    "nn-tile": lambda s: _Gemm("nn", 992, 512, 256, s),
+    "ffn-d256": lambda s: _Ffn(256, 1024, 4096, s),
+    "ffn-d512": lambda s: _Ffn(512, 2048, 4096, s),
+    "ffn-d128": lambda s: _Ffn(128, 512, 4100, s),
+}
+
+
+def _weights(m):
+    return [p for n, p in m.named_parameters() if p.dim() == 2]
+
+
+def _behind_torch(p, values):
+    """Write `values` into p's storage through another tensor: p's version counter does not move."""
+    alias = torch.empty(0, device=DEV).set_(p.untyped_storage(), p.storage_offset(), p.shape, p.stride())
+    alias.copy_(values)
+
+
+@pytest.mark.parametrize("case", list(_PACK_CASES))
+@pytest.mark.parametrize("mutation", ["torch-write", "behind-torch", "fused-adam", "data-assign", "arena-over-registered",
+                                      "load-state-dict-assign", "address-reuse"])
+def test_packs_follow_every_weight_mutation(case, mutation):
+    from openeat_amd import arena as A
+    from openeat_amd.optim import FusedAdam
+    m = _PACK_CASES[case](91)
+    ar = opt = None
+    if mutation == "fused-adam":
+        ar = A.ParamArena(m).activate()
+        opt = FusedAdam(ar, lr=1e-2)
+    m.check()                                                         # registers the packs
+    assert (ops._FFN if case.startswith("ffn") else ops._ROW).entries
+    before = [p.detach().clone() for p in _weights(m)]
+    if mutation == "torch-write":                                     # version counters (no new generation)
+        with torch.no_grad():
+            for p in m.parameters():
+                p.mul_(-0.5)
+    elif mutation == "behind-torch":                                  # a raw write, announced by a bare generation bump
+        vers = [p._version for p in m.parameters()]
+        for p in m.parameters():
+            _behind_torch(p, -0.5 * p.detach())
+        assert [p._version for p in m.parameters()] == vers
+        planes.bump_generation()
+    elif mutation == "fused-adam":                                    # the optimizer's raw kernel (FusedAdam.step -> mark_step)
+        torch.manual_seed(92)
+        ar.grad.normal_()
+        opt.step()
+    elif mutation == "data-assign":                                   # a LIVE Parameter's storage moves
+        for p in m.parameters():
+            p.data = -0.5 * p.detach()
+        planes.new_pass()
+    elif mutation == "arena-over-registered":                         # ParamArena re-points every Parameter, then a raw write
+        ar = A.ParamArena(m).activate()
+        ar.flat.mul_(-0.5)
+        planes.new_pass()
+    elif mutation == "load-state-dict-assign":
+        m.load_state_dict({k: -0.5 * v.detach().clone() for k, v in m.state_dict().items()}, assign=True)
+        planes.new_pass()
+    elif mutation == "address-reuse":                                 # a Parameter dies; a new one with other values on its address
+        landed = []
+        for name in [n for n, p in m.named_parameters() if p.dim() == 2]:
+            old = getattr(m, name)
+            ptr, shape, std = old.data_ptr(), old.shape, float(old.detach().std())
+            setattr(m, name, None)
+            del old
+            gc.collect()
+            keep = []
+            for _ in range(8):
+                cand = torch.nn.Parameter(torch.randn(shape, device=DEV).mul_(std))
+                if cand.data_ptr() == ptr:
+                    break
+                keep.append(cand)
+            landed.append(cand.data_ptr() == ptr)
+            setattr(m, name, cand)
+            del keep
+        print(f"{case}: new Parameters landed on the dead ones' addresses: {landed}")   # (the hazard's precondition; informational)
+        planes.new_pass()
+    after = _weights(m)
+    assert all(not torch.equal(a.detach(), b) for a, b in zip(after, before)), "the mutation changed nothing"
+    assert_pack_rows_live()                                           # before any launch can refresh the tables
+    m.check()
+    if ar is not None:
+        ar.deactivate()
+
+
+@pytest.mark.parametrize("case", ["ffn-d256", "ffn-d128"])
+def test_captured_ffn_refresh_follows_the_weights(case):
+    """The feed-forward's packs (both orientations: the forward's W1 / W2 and the input gradient's W2^T / W1^T) refreshed by a
+    CAPTURED table launch: capture forward + backward, register more feed-forwards, let one die, write the captured weights in
+    place (through torch and behind its back) - every replay must compute with the current values."""
+    m = _PACK_CASES[case](93)
+    other = [_PACK_CASES[case](94 + i) for i in range(3)]
+    m.check()
+    other[0].check()                                                  # two entries: the capture refreshes through the table
+    x = m.x0.clone().requires_grad_()
+    for p in m.params():
+        p.grad = torch.zeros_like(p)
+    x.grad = torch.zeros_like(x)
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    f0, b0 = ops.FFN_FWD_FUSED_LAUNCHES, ops.FFN_BWD_FUSED_LAUNCHES
+    with planes.capture_scope(), torch.cuda.graph(g):
+        planes.new_pass()
+        x.grad.zero_()
+        for p in m.params():
+            p.grad.zero_()
+        y = ops.feed_forward(x, m.w1, m.b1, m.w2, m.b2, ops.ACT_SWISH, residual=x, out_scale=0.5)
+        (y * m.wgt).sum().backward()
+    assert (ops.FFN_FWD_FUSED_LAUNCHES, ops.FFN_BWD_FUSED_LAUNCHES) == (f0 + 1, b0 + 1)
+    assert ops._FFN.event is None and ops._ROW.event is None          # nothing recorded inside the capture survives its scope
+    for o in other[1:]:
+        o.check()                                                     # later registrations
+    del other[1]
+    gc.collect()
+    for write in ("torch", "behind", "torch"):
+        with torch.no_grad():
+            if write == "torch":
+                for p in m.params():
+                    p.mul_(-0.75)
+            else:
+                for p in m.params():
+                    _behind_torch(p, 1.5 * p.detach())
+                planes.bump_generation()
+        ops.pack_tables_sweep()                                       # (what TrainEngine.replay does first)
+        assert_pack_rows_live()
+        g.replay()
+        m.compare([y.detach(), x.grad] + [p.grad for p in m.params()])
+
+
+def test_side_stream_consumers_wait_for_the_latest_ffn_pack():
+    """A consumer on another stream (the right-to-left decoder, the CTC head) orders itself behind the table's recorded event
+    (ops._pack_wait).  That event must be the LATEST pack launch's: the per-entry launch (a weight written through torch while
+    the generation stands) records one too, and an event recorded inside a capture is forgotten when the capture's scope ends."""
+    a, b = _PACK_CASES["ffn-d256"](95), _PACK_CASES["ffn-d256"](96)
+    planes.new_pass()
+    a.check()
+    b.check()
+    ev_table = ops._FFN.event
+    assert ev_table is not None
+    with torch.no_grad():
+        a.w1.mul_(-0.5)                                               # version counter only: a per-entry pack launch
+        a.w2.mul_(1.25)
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    got = a.run()                                                     # the per-entry launches (forward, then input gradient)
+    assert ops._FFN.event is not ev_table and ops._FFN.stream == main, "the per-entry pack launch recorded no event"
+    ev_entry = ops._FFN.event
+    a.compare(got)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        got = a.run()                                                 # fresh packs: the side stream waits on the latest event
+        assert ops._FFN.event is ev_entry
+    main.wait_stream(side)
+    a.compare(got)
+    # ... right after a captured refresh
+    xs = a.x0.clone()
+    gr = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with planes.capture_scope(), torch.cuda.graph(gr):
+        planes.new_pass()
+        with torch.no_grad():
+            ys = ops.feed_forward(xs, a.w1, a.b1, a.w2, a.b2, ops.ACT_SWISH, residual=xs, out_scale=0.5)
+    assert ops._FFN.event is None
+    gr.replay()
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        got = a.run()
+        assert ops._FFN.stream == side
+    main.wait_stream(side)
+    a.compare(got)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(ys, got[0], rtol=1e-5, atol=1e-5)

@@ -36,28 +36,33 @@ TLENS32 = [30] * 8 + [29 - i for i in range(23)] + [4]
 _CACHES = {}
 
 
+def _synth_batch(seconds, tlens):
+    """bench.py::synth_batch's uniform-noise wav through the device fbank, and random targets: (feats, nfr, tgt, tlen)."""
+    g = torch.Generator().manual_seed(0)
+    B = len(seconds)
+    ns = torch.tensor([int(16000 * s) for s in seconds])
+    wav = torch.rand(B, int(ns.max()), generator=g) - 0.5
+    tgt = torch.full((B, max(tlens)), -1, dtype=torch.int32)
+    for b in range(B):
+        wav[b, int(ns[b]):] = 0.0
+        tgt[b, : tlens[b]] = torch.randint(2, V - 1, (tlens[b],), generator=g, dtype=torch.int32)
+    tlen = torch.tensor(tlens, dtype=torch.int32)
+    feats, nfr = Fbank(80, device=DEV)(wav.to(DEV), ns.to(DEV))
+    utt_normalize_(feats, nfr)
+    torch.cuda.synchronize()
+    assert nfr.tolist()[0] == 998 and nfr.tolist()[-1] == 148
+    return feats, nfr, tgt, tlen
+
+
 def _setup(seconds=None, tlens=None):
     seconds, tlens = seconds or SECONDS, tlens or TLENS
     _CACHE = _CACHES.setdefault(len(seconds), {})
     if _CACHE:
         return _CACHE
-    SECONDS_, TLENS_ = seconds, tlens
     torch.manual_seed(777)
     model = ASRModel(80, V, **CONF)
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    g = torch.Generator().manual_seed(0)
-    B = len(SECONDS_)
-    ns = torch.tensor([int(16000 * s) for s in SECONDS_])
-    wav = torch.rand(B, int(ns.max()), generator=g) - 0.5       # bench.py::synth_batch
-    tgt = torch.full((B, max(TLENS_)), -1, dtype=torch.int32)
-    for b in range(B):
-        wav[b, int(ns[b]):] = 0.0
-        tgt[b, : TLENS_[b]] = torch.randint(2, V - 1, (TLENS_[b],), generator=g, dtype=torch.int32)
-    tlen = torch.tensor(TLENS_, dtype=torch.int32)
-    feats, nfr = Fbank(80, device=DEV)(wav.to(DEV), ns.to(DEV))
-    utt_normalize_(feats, nfr)
-    torch.cuda.synchronize()
-    assert nfr.tolist()[0] == 998 and nfr.tolist()[-1] == 148
+    feats, nfr, tgt, tlen = _synth_batch(seconds, tlens)
     # the oracle on the same features (CPU, a few seconds)
     cfg = O.Config(input_size=80, vocab_size=V, **CONF)
     osd = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
@@ -174,6 +179,190 @@ def test_config2_width_training_trajectory_matches_oracle():
     for i, (g, w) in enumerate(zip(got, want)):
         if g is not None:
             assert abs(g - w) <= 2e-4 * abs(w), (i, got, want)
+
+
+# ---- the training trajectory at the rows where the row-block GEMMs, the fused feed-forward, the LayerNorm prologues / epilogue and
+# the packed-weight tables engage (d = 256, precision 6, >= 4096 encoder rows: ops.ROWGEMM_MIN_ROWS, ops.FUSED_FFN_MIN_ROWS) ----------
+# CONF's widths on a shallower model (which kernels engage depends on d and rows, not depth): the CPU oracle stays cheap
+CONF_SHALLOW = dict(CONF, encoder_num_blocks=4, decoder_num_blocks=1, r_decoder_num_blocks=1)
+SECONDS18 = [10.0] * 2 + [9.8 - 0.5 * i for i in range(15)] + [1.5]     # 18 x 248 = 4464 encoder rows; the last one is short
+TLENS18 = [30] * 2 + [29 - i for i in range(15)] + [4]
+TRAJ_STEPS, TRAJ_LR = 6, 1e-3
+_TRAJ = {}
+
+
+def _setup_trajectory():
+    """Initial weights, the batch and the oracle's loss trajectory (forward / backward / clip_grad_norm_ / torch.optim.Adam on the
+    CPU, dropout 0): TRAJ_STEPS steps."""
+    import time
+    if _TRAJ:
+        return _TRAJ
+    torch.manual_seed(779)
+    model = ASRModel(80, V, **CONF_SHALLOW)
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    feats, nfr, tgt, tlen = _synth_batch(SECONDS18, TLENS18)
+    cfg = O.Config(input_size=80, vocab_size=V, **CONF_SHALLOW)
+    osd = {k: v.clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
+    params = [v for v in osd.values() if v.requires_grad]
+    opt = torch.optim.Adam(params, lr=TRAJ_LR)
+    torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
+    t0 = time.perf_counter()
+    want = []
+    for _ in range(TRAJ_STEPS):
+        loss, _ = O.forward(osd, cfg, feats.cpu(), nfr.cpu(), tgt, tlen)
+        opt.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(params, 5.0)
+        opt.step()
+        want.append(float(loss))
+    cpu_s = time.perf_counter() - t0
+    print(f"trajectory oracle: {TRAJ_STEPS} steps in {cpu_s:.1f} s on {torch.get_num_threads()} threads")
+    _TRAJ.update(sd=sd, feats=feats, nfr=nfr, tgt=tgt, tlen=tlen, want=want, cpu_s=cpu_s)
+    return _TRAJ
+
+
+_PACK_COUNTERS = ("LN_FWD_FUSED_LAUNCHES", "LN_BWD_FUSED_LAUNCHES", "LN_EPI_FUSED_LAUNCHES", "ROWGEMM_LAUNCHES", "FFN_FWD_FUSED_LAUNCHES",
+                  "FFN_BWD_FUSED_LAUNCHES")
+
+
+def _trajectory_model(c):
+    """The model in precision 6 after ONE no-grad pass at the batch's rows (a CTC-greedy decode): the packed-weight tables hold rows
+    at the Parameters' own addresses before anything re-points them - the real-world order (a decode before training)."""
+    from openeat_amd import ops
+    model = ASRModel(80, V, **CONF_SHALLOW)
+    model.load_state_dict(c["sd"])
+    model = model.to(DEV).eval()
+    with torch.no_grad():
+        model.ctc_greedy_search(c["feats"], c["nfr"])
+    torch.cuda.synchronize()
+    assert ops._ROW.entries and ops._FFN.entries, "the decode registered no packed weights: the rows are below the kernels' threshold"
+    return model.train()
+
+
+def _count_parked_layernorms(monkeypatch):
+    """Wrap ops.resolve_pending_ln / resolve_pending_lnf: the list receives every count of parked LayerNorms they had to launch
+    late (a non-zero count after a step means some consumer read the LayerNorm's output before it was written)."""
+    from openeat_amd import ops
+    late = []
+    for name in ("resolve_pending_ln", "resolve_pending_lnf"):
+        def wrapped(orig=getattr(ops, name), name=name):
+            n = orig()
+            late.append((name, n))
+            return n
+        monkeypatch.setattr(ops, name, wrapped)
+    return late
+
+
+def _flush_parked(late):
+    from openeat_amd import ops
+    ops.resolve_pending_ln()
+    ops.resolve_pending_lnf()
+    late.clear()
+
+
+def _assert_nothing_parked(late, what):
+    from openeat_amd import ops
+    ops.resolve_pending_ln()                                       # the sweep, now: what did the step leave?
+    ops.resolve_pending_lnf()
+    assert all(n == 0 for _, n in late), (what, late)
+    late.clear()
+
+
+def _restore(old_prec):
+    from openeat_amd import hip, ops
+    hip.GEMM_PRECISION = old_prec
+    ops.set_seed_device_counter(None)
+    ops.PARALLEL_DECODERS = False
+    ops.POS_PROJ_AHEAD = False
+
+
+def test_config2_width_training_trajectory_at_bench_rows_matches_oracle(monkeypatch):
+    """TrainEngine (static shapes, parallel decoders, precision 6) at 4464 encoder rows after a decode registered the packs: one
+    eager step, capture (its warm-up step is real), three replays, drop the graph (empty_cache), one more eager step - every
+    observable loss within 2e-4 relative of the oracle's trajectory.  The packed-weight tables hold no row of freed storage after
+    the engine re-points the weights nor after the graph's memory went back (tests/packcheck.py, checked before any launch)."""
+    from openeat_amd import hip, ops, planes
+    from openeat_amd.engine import TrainEngine
+    from packcheck import assert_pack_rows_live
+    c = _setup_trajectory()
+    late = _count_parked_layernorms(monkeypatch)
+    old = hip.GEMM_PRECISION
+    hip.GEMM_PRECISION = 6
+    batch = dict(features=c["feats"], features_length=c["nfr"], targets=c["tgt"].to(DEV), targets_length=c["tlen"].to(DEV))
+    got, moved = [], None
+    eng = None
+    try:
+        model = _trajectory_model(c)
+        eng = TrainEngine(model, lr=TRAJ_LR, grad_clip=5.0, static_shapes=True, parallel_decoders=True)
+        planes.new_pass()
+        assert_pack_rows_live()
+        _flush_parked(late)                                        # (what the decode left: not a training step)
+        c0 = {k: getattr(ops, k) for k in _PACK_COUNTERS}
+        got.append(float(eng.step(batch)[0]))                      # step 1: eager
+        moved = {k: getattr(ops, k) - c0[k] for k in _PACK_COUNTERS}
+        _assert_nothing_parked(late, "eager step 1")
+        eng.capture(batch, warmup=1)                               # step 2: the capture's warm-up step (a real step)
+        got.append(None)
+        for _ in range(3):
+            got.append(float(eng.replay()[0]))                     # steps 3-5 from the graph
+        torch.cuda.synchronize()
+        eng.drop_graph()                                           # (torch.cuda.empty_cache: freed storage may be unmapped now)
+        planes.new_pass()
+        assert_pack_rows_live()
+        got.append(float(eng.step(batch)[0]))                      # step 6: eager again
+        torch.cuda.synchronize()
+        _assert_nothing_parked(late, "eager step 6")
+    finally:
+        _restore(old)
+        if eng is not None:
+            eng.arena.deactivate()
+    want = c["want"]
+    rel = [None if g is None else abs(g - w) / abs(w) for g, w in zip(got, want)]
+    print("trajectory at 4464 rows: oracle", [round(w, 4) for w in want], "hip", [None if g is None else round(g, 4) for g in got],
+          "rel", [None if r is None else f"{r:.2e}" for r in rel], f"oracle CPU {c['cpu_s']:.1f} s")
+    assert all(v > 0 for v in moved.values()), moved               # the kernels under test really ran in the eager step
+    assert want[-1] < 0.8 * want[0], want                          # the model is really learning this batch
+    for i, r in enumerate(rel):
+        assert r is None or r <= 2e-4, (i, got, want)
+
+
+def test_config2_width_reference_loop_at_bench_rows_matches_oracle(monkeypatch):
+    """The reference-shaped loop outside the engine (ParamArena + FusedAdam + model(**batch) + backward()) at the same rows, after
+    the same decode: the packs follow the arena's re-pointing and the optimizer's raw writes - losses on the oracle's trajectory."""
+    from openeat_amd import hip, ops, planes
+    from openeat_amd.arena import ParamArena
+    from openeat_amd.optim import FusedAdam
+    from packcheck import assert_pack_rows_live
+    c = _setup_trajectory()
+    late = _count_parked_layernorms(monkeypatch)
+    old = hip.GEMM_PRECISION
+    hip.GEMM_PRECISION = 6
+    batch = dict(features=c["feats"], features_length=c["nfr"], targets=c["tgt"].to(DEV), targets_length=c["tlen"].to(DEV))
+    got, ar = [], None
+    try:
+        model = _trajectory_model(c)
+        ar = ParamArena(model).activate()
+        opt = FusedAdam(ar, lr=TRAJ_LR, max_grad_norm=5.0)
+        planes.new_pass()
+        assert_pack_rows_live()
+        _flush_parked(late)                                        # (what the decode left: not a training step)
+        for step in range(4):
+            opt.zero_grad()
+            loss, _ = model(**batch)
+            loss.backward()
+            ops.join_side_stream()
+            opt.step()
+            got.append(float(loss))
+            _assert_nothing_parked(late, f"step {step + 1}")
+        torch.cuda.synchronize()
+    finally:
+        _restore(old)
+        if ar is not None:
+            ar.deactivate()
+    want = c["want"][:len(got)]
+    print("reference loop at 4464 rows: oracle", [round(w, 4) for w in want], "hip", [round(g, 4) for g in got])
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert abs(g - w) <= 2e-4 * abs(w), (i, got, want)
 
 
 # ---- BASELINE.json configs[4]'s model: 24-layer Conformer d = 512 (h = 8, ff = 2048, K = 15; SURVEY 8d's assumed widths) ----------

@@ -297,3 +297,55 @@ def test_gpu_files_are_collected_kernel_proofs_first():
     here = os.path.dirname(os.path.abspath(__file__))
     present = sorted(f for f in os.listdir(here) if f.startswith("test_gpu_") and f.endswith(".py"))
     assert set(present) <= set(order), f"add {set(present) - set(order)} to conftest._GPU_FILE_ORDER"
+
+
+def test_pack_table_dead_row_predicates():
+    """ops._row_dead / ops._ffn_dead (host logic only): a packed-weight row is dead when its owner is gone OR when the owner lives
+    on at another address (`p.data = ...`: ParamArena, load_state_dict-style re-pointing) - a sweep that looked at the owner's
+    life alone kept refreshing from the freed old storage.  Only the untouched rows survive a sweep."""
+    import gc
+    import weakref
+    from openeat_amd import ops
+
+    def row_ent(p):
+        return dict(owner=weakref.ref(p), off=0)
+
+    ps = {name: torch.nn.Parameter(torch.randn(8, 8)) for name in ("deleted", "repointed", "untouched")}
+    tab = ops._PackTable(6)
+    keys = {}
+    for name, p in ps.items():
+        keys[name] = (p.data_ptr(), 8, 8, 8, 0)
+        assert tab.add(keys[name], [p.data_ptr(), 0, 8, 8, 8, 0], row_ent(p), "cpu")
+    # (a view's row: its source address sits `off` bytes into the owner)
+    keys["view"] = (ps["untouched"].data_ptr() + 4 * 8, 7, 8, 8, 0)
+    assert tab.add(keys["view"], [keys["view"][0], 0, 7, 8, 8, 0], dict(owner=weakref.ref(ps["untouched"]), off=4 * 8), "cpu")
+    assert not any(ops._row_dead(k, tab.entries[k]) for k in keys.values())
+    del ps["deleted"]
+    gc.collect()
+    moved = ps["repointed"]
+    moved.data = torch.randn(8, 8)                         # a live Parameter whose storage moved
+    assert moved.data_ptr() != keys["repointed"][0]
+    assert ops._row_dead(keys["deleted"], tab.entries[keys["deleted"]])
+    assert ops._row_dead(keys["repointed"], tab.entries[keys["repointed"]])
+    assert not ops._row_dead(keys["untouched"], tab.entries[keys["untouched"]])
+    assert not ops._row_dead(keys["view"], tab.entries[keys["view"]])
+    tab.sweep(ops._row_dead)
+    assert set(tab.entries) == {keys["untouched"], keys["view"]}
+    live = {int(tab.host[i, 0]) for i in range(tab.n) if int(tab.host[i, 0])}
+    assert live == {keys["untouched"][0], keys["view"][0]}     # the dead rows are neutralised (source pointer 0), not removed
+    assert tab.n == 4
+
+    w = {name: (torch.nn.Parameter(torch.randn(16, 8)), torch.nn.Parameter(torch.randn(8, 16))) for name in ("deleted", "repointed", "untouched")}
+    ftab = ops._PackTable(9)
+    fkeys = {}
+    for name, (w1, w2) in w.items():
+        fkeys[name] = (w1.data_ptr(), w2.data_ptr(), 6)
+        assert ftab.add(fkeys[name], [w1.data_ptr(), w2.data_ptr(), 0, 0, 0, 0, 8, 16, 3], dict(w1=weakref.ref(w1), w2=weakref.ref(w2)), "cpu")
+    del w["deleted"]
+    gc.collect()
+    w["repointed"][1].data = torch.randn(8, 16)            # W2 alone moves: the row is dead all the same
+    for name, dead in (("deleted", True), ("repointed", True), ("untouched", False)):
+        assert ops._ffn_dead(fkeys[name], ftab.entries[fkeys[name]]) == dead, name
+    ftab.sweep(ops._ffn_dead)
+    assert set(ftab.entries) == {fkeys["untouched"]}
+    assert [int(ftab.host[i, 0]) for i in range(ftab.n)] == [0, 0, fkeys["untouched"][0]]
