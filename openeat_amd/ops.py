@@ -55,12 +55,37 @@ def _chk(t: torch.Tensor, name: str, keep_pending: bool = False) -> torch.Tensor
     if not t.is_cuda or t.dtype != torch.float32:
         raise TypeError(f"{name}: openeat_amd ops need float32 CUDA tensors (got {t.dtype} on {t.device}); "
                         "there is no CPU fallback")
-    if _PENDING_LNF and not keep_pending:
+    if not keep_pending:
         # the output of a parked LayerNorm forward (PreNormFn) reaching an op that does not make it itself: launch it now
-        pend = _PENDING_LNF.pop(t.data_ptr(), None)
+        pend = _PENDING_LNF.take(t)
         if pend is not None:
-            _resolve_lnf(pend)
+            pend.resolve()
     return t.contiguous()
+
+
+class _ParkRegistry:
+    """Parked LayerNorm launches (_LnFwdPark / _LnBwdPark) keyed by the address of their entry's output `attr` (forward y, backward g)."""
+
+    def __init__(self, attr):
+        self.attr, self._by_addr = attr, {}
+
+    def __len__(self):
+        return len(self._by_addr)
+
+    def park(self, entry):
+        self._by_addr[getattr(entry, self.attr).data_ptr()] = entry
+
+    def take(self, t):
+        """The entry parked on t's address (removed), or None."""
+        return self._by_addr.pop(t.data_ptr(), None) if self._by_addr else None
+
+    def sweep(self):
+        """Launch every entry that nobody launched, forget them all; returns how many were launched."""
+        late = [e for e in self._by_addr.values() if not e.done]
+        for e in late:
+            e.resolve()
+        self._by_addr.clear()
+        return len(late)
 
 
 # The LayerNorm FORWARD of a pre-norm fork as the prologue of the GEMM that consumes it (oe_rowgemm6 / oe_ffn_fwd's lnf arguments):
@@ -71,33 +96,42 @@ def _chk(t: torch.Tensor, name: str, keep_pending: bool = False) -> torch.Tensor
 # launched where the step's bookkeeping is reset (predrop_clear).  36 launches per step at config 2.
 LN_FWD_FUSE = os.environ.get("OE_LN_FWD_FUSE", "1") == "1"
 LN_FWD_FUSED_LAUNCHES = 0       # (tests)
-_PENDING_LNF = {}
-
-
-def _resolve_lnf(pend):
-    if pend.get("done"):
-        return
-    pend["done"] = True
-    if pend.get("gamma2") is not None:
-        hip.call("oe_layernorm_pair_fwd", pend["x"], pend["gamma"], pend["beta"], pend["eps"], pend["gamma2"], pend["beta2"], pend["eps2"], pend["rows"],
-                 pend["d"], pend["u"], pend["stats"], pend["y"], pend["stats2"])
-        return
-    _ln_fwd(pend["x"], pend["gamma"], pend["beta"], pend["eps"], pend["rows"], pend["d"], pend["rowmask"], ACT_NONE, pend["y"], pend["stats"])
+_PENDING_LNF = _ParkRegistry("y")
 
 
 def resolve_pending_lnf():
-    n = 0
-    for pend in list(_PENDING_LNF.values()):
-        if not pend.get("done"):
-            _resolve_lnf(pend)
-            n += 1
-    _PENDING_LNF.clear()
-    return n
+    return _PENDING_LNF.sweep()
 
 
-def _lnf_take(t):
-    """The parked LayerNorm forward whose output is t (removed from the registry), or None."""
-    return _PENDING_LNF.pop(t.data_ptr(), None) if _PENDING_LNF else None
+class _LnFwdPark:
+    """A parked LayerNorm forward: y = LN(x) (PreNormFn), or the pair form u = LN1(x), y = LN2(u) (NormPairFn)."""
+    __slots__ = ("x", "gamma", "beta", "eps", "rows", "d", "y", "stats", "rowmask", "gamma2", "beta2", "eps2", "u", "stats2", "done")
+
+    def __init__(self, x, gamma, beta, eps, rows, d, y, stats, rowmask=None, gamma2=None, beta2=None, eps2=None, u=None, stats2=None):
+        self.x, self.gamma, self.beta, self.eps, self.rows, self.d, self.y, self.stats = x, gamma, beta, eps, rows, d, y, stats
+        self.rowmask, self.gamma2, self.beta2, self.eps2, self.u, self.stats2 = rowmask, gamma2, beta2, eps2, u, stats2
+        self.done = False
+
+    def resolve(self):
+        """The LayerNorm as a launch of its own (exactly what PreNormFn / NormPairFn.forward would have launched)."""
+        if self.done:
+            return
+        self.done = True
+        if self.gamma2 is not None:
+            hip.call("oe_layernorm_pair_fwd", self.x, self.gamma, self.beta, self.eps, self.gamma2, self.beta2, self.eps2, self.rows, self.d,
+                     self.u, self.stats, self.y, self.stats2)
+        else:
+            _ln_fwd(self.x, self.gamma, self.beta, self.eps, self.rows, self.d, self.rowmask, ACT_NONE, self.y, self.stats)
+
+    def prologue(self):
+        """The `lnf` argument of hip.rowgemm6 / hip.ffn_fwd (LnfPrologue.fill)."""
+        return dict(x=self.x, gamma=self.gamma, beta=self.beta, eps=self.eps, y=self.y, stats=self.stats, rowmask=self.rowmask,
+                    gamma2=self.gamma2, beta2=self.beta2, eps2=self.eps2, u=self.u, stats2=self.stats2)
+
+    def fused(self):
+        global LN_FWD_FUSED_LAUNCHES
+        self.done = True
+        LN_FWD_FUSED_LAUNCHES += 1
 
 
 def _new(*shape, like: torch.Tensor, zero=False):
@@ -284,9 +318,9 @@ def _rowgemm_try(x, w, transposed, bias, out, epi, ln_pending=None, lnf_pending=
         return _rowgemm_try_impl(x, w, transposed, bias, out, epi, ln_pending, lnf_pending, ln_epi)
     finally:
         if ln_pending is not None:
-            _resolve_ln(ln_pending)              # (no-op when the fused launch has happened)
+            ln_pending.resolve()                 # (no-op when the fused launch has happened)
         if lnf_pending is not None:
-            _resolve_lnf(lnf_pending)
+            lnf_pending.resolve()
 
 
 def _rowgemm_try_impl(x, w, transposed, bias, out, epi, ln_pending, lnf_pending=None, ln_epi=None):
@@ -326,25 +360,22 @@ def _rowgemm_try_impl(x, w, transposed, bias, out, epi, ln_pending, lnf_pending=
         out = _new(M, n, like=x)
     elif out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % 16:
         return None
-    global ROWGEMM_LAUNCHES, LN_BWD_FUSED_LAUNCHES
+    global ROWGEMM_LAUNCHES
     ROWGEMM_LAUNCHES += 1
-    ln = None
-    if ln_pending is not None and not ln_pending.get("done"):
-        pd = ln_pending
+    ln = lnf = None
+    if ln_pending is not None and not ln_pending.done:
         sd = epi.get("seed_dev")
-        if (form == 1 and k == 256 and x.is_contiguous() and x.data_ptr() == pd["g"].data_ptr() and M == pd["rows"] and
+        if (form == 1 and k == 256 and x.is_contiguous() and x.data_ptr() == ln_pending.g.data_ptr() and M == ln_pending.rows and
                 (sd is None or _seed_dev is None or sd.data_ptr() == _seed_dev.data_ptr()) and (epi.get("drop_p", 0.0) or 0.0) == 0.0):
-            ln = _ln_dict(pd)
+            ln = ln_pending.prologue()
         else:
-            _resolve_ln(pd)                     # this launch reads x: the LayerNorm backward first, on its own
-    lnf = None
-    if lnf_pending is not None and not lnf_pending.get("done"):
+            ln_pending.resolve()                # this launch reads x: the LayerNorm backward first, on its own
+    if lnf_pending is not None and not lnf_pending.done:
         q = lnf_pending
-        if (form == 1 and k == 256 and ln is None and x.is_contiguous() and x.data_ptr() == q["y"].data_ptr() and M == q["rows"] and
-                q.get("gamma2") is None):
-            lnf = dict(x=q["x"], gamma=q["gamma"], beta=q["beta"], eps=q["eps"], y=q["y"], stats=q["stats"], rowmask=q["rowmask"])
+        if form == 1 and k == 256 and ln is None and x.is_contiguous() and x.data_ptr() == q.y.data_ptr() and M == q.rows and q.gamma2 is None:
+            lnf = q.prologue()
         else:
-            _resolve_lnf(q)                     # this launch reads x: the LayerNorm first, on its own
+            q.resolve()                         # this launch reads x: the LayerNorm first, on its own
     lne = None
     if (ln_epi is not None and form == 1 and k == 256 and n == 256 and lnf is None and bias is None and not epi and
             M == ln_epi["dx"].shape[0] and ln_epi["dx"].is_contiguous() and ln_epi["x"].is_contiguous()):
@@ -356,13 +387,9 @@ def _rowgemm_try_impl(x, w, transposed, bias, out, epi, ln_pending, lnf_pending=
     if lne is not None:
         ln_epi["done"] = True
     if ln is not None:
-        ln_pending["done"] = True
-        LN_BWD_FUSED_LAUNCHES += 1
-        _ln_reduce(ln_pending)
+        ln_pending.fused()
     if lnf is not None:
-        global LN_FWD_FUSED_LAUNCHES
-        lnf_pending["done"] = True
-        LN_FWD_FUSED_LAUNCHES += 1
+        lnf_pending.fused()
     return out
 
 
@@ -370,13 +397,13 @@ def gemm_nt(x, w, bias=None, out=None, out_planes=False, **epi):
     """y[M,N] = x[M,K] @ w[N,K]^T (+ epilogue).  out_planes: the output is a later GEMM's operand - write its bf16 planes too."""
     M, K = x.shape
     N = w.shape[0]
-    lnf = _lnf_take(x)                                                            # x may be the output of a parked LayerNorm forward
+    lnf = _PENDING_LNF.take(x)                                                    # x may be the output of a parked LayerNorm forward
     if not (out_planes and _planes.split_activations()):
         y = _rowgemm_try(x, w, False, bias, out, epi, lnf_pending=lnf)             # (launches or resolves it on every path)
         if y is not None:
             return y
     elif lnf is not None:
-        _resolve_lnf(lnf)
+        lnf.resolve()
     if out is None:
         out = _new(M, N, like=x)
     ap, bp = _operand_planes(x, w)
@@ -390,13 +417,13 @@ def gemm_nn(dy, w, out=None, out_planes=False, ln_epi=None, **epi):
     operands exist at all (the conv front end's policy)."""
     M, N = dy.shape
     K = w.shape[1]
-    pend = _PENDING_LN.pop(dy.data_ptr(), None) if _PENDING_LN else None         # dy is the g of a parked LayerNorm backward
+    pend = _PENDING_LN.take(dy)                                                   # dy is the g of a parked LayerNorm backward
     if not (out_planes and (_planes.available() if out_planes == "always" else _planes.split_activations())):
         y = _rowgemm_try(dy, w, True, None, out, epi, ln_pending=pend, ln_epi=ln_epi)      # (launches or resolves it on every path)
         if y is not None:
             return y
     elif pend is not None:
-        _resolve_ln(pend)
+        pend.resolve()
     if out is None:
         out = _new(M, K, like=dy)
     ap, bp = _operand_planes(dy, w)
@@ -652,8 +679,8 @@ def _group_wgrads(descs):
         return set()
     host, total = plan
     table = torch.empty(len(host), dtype=torch.uint8, device=descs[idx[0]]["dy"].device)
-    if LN_TABLE is not None and not LN_TABLE.get("eager"):
-        LN_TABLE.setdefault("uploads", []).append((table, host))       # inside a capture: filled by ln_table_end, kept with the graph
+    if LN_TABLE is not None and not LN_TABLE.eager:
+        LN_TABLE.uploads.append((table, host))                         # inside a capture: filled by ln_table_end, kept with the graph
     else:
         # stream-ordered upload from pinned memory: the host never waits for the stream (bench.py's bracketed steps park the GPU
         # while the host enqueues the whole step)
@@ -807,10 +834,25 @@ def _ln_fwd(x, gamma, beta, eps, rows, d, rowmask, act, y, stats, planes_out=Tru
 # parameter-gradient partials to ONE table-driven launch at the end of backward (ln_table_flush) instead of one small
 # launch per call.  The table is a device tensor allocated before the capture; the host fills it after the capture (the
 # workspaces' addresses inside the graph's memory pool are the same at every replay).
-LN_TABLE = None
 LN_TABLE_CAPACITY = 512
 
 
+class _LnTable:
+    """The reduce table of one step: rows (workspace, rows, d, dgamma, dbeta) of oe_layernorm_param_reduce_table; keep: the
+    workspaces of the rows since the last flush; uploads: (device table, host bytes) of grouped weight-gradient launches (_group_wgrads)."""
+    __slots__ = ("dev", "eager", "entries", "keep", "max_rows", "max_d", "launched", "uploads")
+
+    def __init__(self, dev, eager):
+        self.dev, self.eager, self.entries, self.keep, self.uploads = dev, eager, [], [], []
+        self.max_rows, self.max_d, self.launched = 1, 4, 0
+
+    def add(self, ws, rows, d, dg, db):
+        self.entries.append((ws.data_ptr(), rows, d, dg.data_ptr(), db.data_ptr()))
+        self.keep.append(ws)
+        self.max_rows, self.max_d = max(self.max_rows, rows), max(self.max_d, d)
+
+
+LN_TABLE = None             # an _LnTable in table mode
 LN_EAGER_TABLE = os.environ.get("OE_LN_EAGER_TABLE", "1") == "1"
 _LN_EAGER_DEV = {}          # device -> the eager table's device tensor (allocated once)
 _LN_EAGER_PINNED = []       # pinned host tables of the last flushes (alive until their stream-ordered uploads have surely run)
@@ -826,7 +868,7 @@ def ln_table_begin(device, eager=False):
             dev = _LN_EAGER_DEV[device] = torch.zeros(LN_TABLE_CAPACITY, 5, dtype=torch.int64, device=device)
     else:
         dev = torch.zeros(LN_TABLE_CAPACITY, 5, dtype=torch.int64, device=device)
-    LN_TABLE = {"dev": dev, "entries": [], "keep": [], "max_rows": 1, "max_d": 4, "launched": 0, "eager": eager}
+    LN_TABLE = _LnTable(dev, eager)
     return LN_TABLE
 
 
@@ -834,33 +876,41 @@ def ln_table_flush():
     """Enqueue the reduction of everything recorded since the last flush (current stream; call after the side streams
     have been joined)."""
     t = LN_TABLE
-    if t is None or len(t["entries"]) == t["launched"]:
+    if t is None or len(t.entries) == t.launched:
         return
-    first, n = t["launched"], len(t["entries"]) - t["launched"]
-    assert len(t["entries"]) <= LN_TABLE_CAPACITY, "LN_TABLE_CAPACITY exceeded"
-    if t.get("eager"):
-        host = torch.tensor(t["entries"][first:], dtype=torch.int64).pin_memory()
-        t["dev"][first:first + n].copy_(host, non_blocking=True)
+    first, n = t.launched, len(t.entries) - t.launched
+    assert len(t.entries) <= LN_TABLE_CAPACITY, "LN_TABLE_CAPACITY exceeded"
+    if t.eager:
+        host = torch.tensor(t.entries[first:], dtype=torch.int64).pin_memory()
+        t.dev[first:first + n].copy_(host, non_blocking=True)
         _LN_EAGER_PINNED.append(host)
         del _LN_EAGER_PINNED[:-8]
         cur = torch.cuda.current_stream()
-        for ws in t["keep"]:
+        for ws in t.keep:
             ws.record_stream(cur)               # (workspaces of norms that ran on the decoders' streams)
-    hip.call("oe_layernorm_param_reduce_table", t["dev"][first:], n, t["max_rows"], t["max_d"])
-    t["launched"] = len(t["entries"])
-    t["keep"] = []                      # later allocations may reuse the workspaces: they come after this launch in stream order
+    hip.call("oe_layernorm_param_reduce_table", t.dev[first:], n, t.max_rows, t.max_d)
+    t.launched = len(t.entries)
+    t.keep = []                         # later allocations may reuse the workspaces: they come after this launch in stream order
 
 
 def ln_table_end():
     """After the capture: upload the table (host -> device copy, not capturable) and leave table mode."""
     global LN_TABLE
     t, LN_TABLE = LN_TABLE, None
-    if t is not None and t["entries"]:
-        t["dev"][: len(t["entries"])].copy_(torch.tensor(t["entries"], dtype=torch.int64))
+    if t is not None and t.entries:
+        t.dev[: len(t.entries)].copy_(torch.tensor(t.entries, dtype=torch.int64))
     if t is not None:
-        for table, host in t.get("uploads", ()):        # grouped weight-gradient tables recorded during the capture
+        for table, host in t.uploads:           # grouped weight-gradient tables recorded during the capture
             table.copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
     return t
+
+
+def _ln_param_reduce(ws, rows, d, dg, db, to_arena):
+    """A LayerNorm backward's parameter-gradient partials: a row of the active table (arena gradients only), or a reduce launch now."""
+    if LN_TABLE is not None and to_arena:
+        LN_TABLE.add(ws, rows, d, dg, db)
+    else:
+        hip.call("oe_layernorm_param_reduce", ws, rows, d, dg, db)
 
 
 # A block's output is `residual + out_scale * dropout(f(LN(x)))`, and the LayerNorm that consumes it belongs to the NEXT block:
@@ -879,10 +929,8 @@ _PREDROP = {}
 def predrop_clear():
     """Called where a new step starts (ASRModel.forward / LanguageModel.forward / TrainEngine): drops the previous step's
     leftovers - dropped-gradient copies and the registry of pre-split GEMM operands."""
-    if _PENDING_LN:
-        resolve_pending_ln()
-    if _PENDING_LNF:
-        resolve_pending_lnf()
+    resolve_pending_ln()
+    resolve_pending_lnf()
     _PREDROP.clear()
     _planes.clear()
 
@@ -900,61 +948,81 @@ def _tag_out_drop(out, out_scale, p_out, s_out, rowmask=None, ln_fuse=False):
 # `g = _out_drop_grad(dy)` followed by `gemm_nn(g, w)` on the row-block kernel (_ln_fuse_ok); the pre-norm fork that consumes the
 # block's output then does NOT launch its backward kernel but parks its arguments here, keyed by the address of g; gemm_nn finds
 # them and launches the fused kernel, which writes dx and g before anything else can read them.  Every other path out of
-# _out_drop_grad / gemm_nn resolves a parked entry by launching the LayerNorm backward on its own (_resolve_ln), and TrainEngine
-# checks that none is left behind.  24 launches per step at config 2 (10.8 us + a dependent-launch gap each).
+# _out_drop_grad / gemm_nn resolves a parked entry by launching the LayerNorm backward on its own (_LnBwdPark.resolve), and
+# TrainEngine checks that none is left behind.  24 launches per step at config 2 (10.8 us + a dependent-launch gap each).
 LN_BWD_FUSE = os.environ.get("OE_LN_BWD_FUSE", "1") == "1"
 LN_BWD_FUSED_LAUNCHES = 0       # (tests)
 LN_EPI_FUSE = os.environ.get("OE_LN_EPI_FUSE", "1") == "1"      # the conv module's norm backward as an epilogue (ConvModuleFn.backward)
 LN_EPI_FUSED_LAUNCHES = 0
-_PENDING_LN = {}
-
-
-def _ln_fuse_ok(rows, d, w):
-    """Forward-time promise of a block whose backward starts with gemm_nn(g, w), w (d, d): will that be the k = 256 row-block kernel?"""
-    return (LN_BWD_FUSE and ROWGEMM and FUSE_OUT_DROP and hip.GEMM_PRECISION == 6 and d == 256 and rows >= ROWGEMM_MIN_ROWS and
-            w.shape[0] == 256 and w.shape[1] == 256 and not _planes.active())
-
-
-def _ln_reduce(pend):
-    if pend["table"]:
-        return                                   # (a captured step: the entries are in LN_TABLE, one launch at the end of backward)
-    hip.call("oe_layernorm_param_reduce", pend["ws"], pend["rows"], pend["d"], pend["dg"], pend["db"])
-    if pend.get("gamma2") is not None:
-        hip.call("oe_layernorm_param_reduce", pend["ws2"], pend["rows"], pend["d"], pend["dg2"], pend["db2"])
-
-
-def _ln_dict(pend):
-    """A parked LayerNorm backward as the `ln` argument of hip.rowgemm6 / hip.ffn_bwd (LnPrologue.fill)."""
-    alpha, p, seed, gmask = pend["spec"]
-    return dict(dy=pend["dy"], x=pend["x"], stats=pend["stats"], gamma=pend["gamma"], add=pend["add"], dx=pend["dx"], g=pend["g"], ws=pend["ws"],
-                alpha=alpha, p=p, seed=seed, rowmask=gmask, ln_rowmask=pend.get("rowmask"), beta=pend["beta"] if pend.get("gamma2") is not None else None,
-                gamma2=pend.get("gamma2"), stats2=pend.get("stats2"), ws2=pend.get("ws2"))
-
-
-def _resolve_ln(pend):
-    """The parked LayerNorm backward as a launch of its own (exactly what _ln_bwd / NormPairFn.backward would have launched)."""
-    if pend.get("done"):
-        return
-    alpha, p, seed, gmask = pend["spec"]
-    if pend.get("gamma2") is not None:
-        hip.call("oe_layernorm_pair_bwd_dx_drop", pend["dy"], pend["x"], pend["gamma"], pend["beta"], pend["stats"], pend["gamma2"], pend["stats2"],
-                 pend["rows"], pend["d"], pend["add"], pend["dx"], pend["g"], alpha, p, seed, _seed_dev, gmask, pend["ws"], pend["ws2"])
-    else:
-        hip.call("oe_layernorm_bwd_dx_drop", pend["dy"], pend["x"], pend["gamma"], pend["beta"], 0, pend["stats"], pend["rows"], pend["d"],
-                 pend.get("rowmask"), pend["add"], pend["dx"], pend["g"], alpha, p, seed, _seed_dev, gmask, pend["ws"])
-    pend["done"] = True
-    _ln_reduce(pend)
+_PENDING_LN = _ParkRegistry("g")
 
 
 def resolve_pending_ln():
     """Safety net (TrainEngine after backward, predrop_clear): a parked LayerNorm backward nobody picked up.  Returns the count."""
-    n = 0
-    for pend in list(_PENDING_LN.values()):
-        if not pend.get("done"):
-            _resolve_ln(pend)
-            n += 1
-    _PENDING_LN.clear()
-    return n
+    return _PENDING_LN.sweep()
+
+
+def _ln_rows_fusable(rows, d):
+    """Rows the k = 256 row-block kernels can make with a LayerNorm prologue / epilogue (each site adds its switches and conditions)."""
+    return hip.GEMM_PRECISION == 6 and d == 256 and rows >= ROWGEMM_MIN_ROWS and not _planes.active()
+
+
+def _ln_fuse_ok(rows, d, w):
+    """Forward-time promise of a block whose backward starts with gemm_nn(g, w), w (d, d): will that be the k = 256 row-block kernel?"""
+    return LN_BWD_FUSE and ROWGEMM and FUSE_OUT_DROP and _ln_rows_fusable(rows, d) and w.shape[0] == 256 and w.shape[1] == 256
+
+
+class _LnBwdPark:
+    """A parked LayerNorm backward (_ln_bwd), or the pair form (NormPairFn.backward: LN1 with beta, LN2 with gamma2 / stats2 / ws2).
+    Its parameter-gradient partials become rows of LN_TABLE if one is active when it is parked (made: the rows belong to the
+    ln_table_flush that follows the norm's own backward, wherever it is launched), else they are reduced when it is launched."""
+    __slots__ = ("dy", "x", "gamma", "beta", "stats", "add", "dx", "g", "ws", "spec", "rows", "d", "dg", "db", "rowmask",
+                 "gamma2", "stats2", "ws2", "dg2", "db2", "table", "done")
+
+    def __init__(self, dy, x, gamma, beta, stats, add, dx, g, ws, spec, rows, d, dg, db, rowmask=None,
+                 gamma2=None, stats2=None, ws2=None, dg2=None, db2=None):
+        self.dy, self.x, self.gamma, self.beta, self.stats, self.add, self.dx, self.g = dy, x, gamma, beta, stats, add, dx, g
+        self.ws, self.spec, self.rows, self.d, self.dg, self.db, self.rowmask = ws, spec, rows, d, dg, db, rowmask
+        self.gamma2, self.stats2, self.ws2, self.dg2, self.db2 = gamma2, stats2, ws2, dg2, db2
+        self.table, self.done = LN_TABLE is not None, False
+        if self.table:
+            for args in self._partials():
+                LN_TABLE.add(*args)
+
+    def _partials(self):
+        one = (self.ws, self.rows, self.d, self.dg, self.db)
+        return (one,) if self.gamma2 is None else (one, (self.ws2, self.rows, self.d, self.dg2, self.db2))
+
+    def _launched(self):
+        self.done = True
+        if not self.table:
+            for args in self._partials():
+                hip.call("oe_layernorm_param_reduce", *args)
+
+    def resolve(self):
+        """The LayerNorm backward as a launch of its own (exactly what _ln_bwd / NormPairFn.backward would have launched)."""
+        if self.done:
+            return
+        alpha, p, seed, gmask = self.spec
+        if self.gamma2 is not None:
+            hip.call("oe_layernorm_pair_bwd_dx_drop", self.dy, self.x, self.gamma, self.beta, self.stats, self.gamma2, self.stats2,
+                     self.rows, self.d, self.add, self.dx, self.g, alpha, p, seed, _seed_dev, gmask, self.ws, self.ws2)
+        else:
+            hip.call("oe_layernorm_bwd_dx_drop", self.dy, self.x, self.gamma, self.beta, 0, self.stats, self.rows, self.d,
+                     self.rowmask, self.add, self.dx, self.g, alpha, p, seed, _seed_dev, gmask, self.ws)
+        self._launched()
+
+    def prologue(self):
+        """The `ln` argument of hip.rowgemm6 / hip.ffn_bwd (LnPrologue.fill)."""
+        alpha, p, seed, gmask = self.spec
+        return dict(dy=self.dy, x=self.x, stats=self.stats, gamma=self.gamma, add=self.add, dx=self.dx, g=self.g, ws=self.ws,
+                    alpha=alpha, p=p, seed=seed, rowmask=gmask, ln_rowmask=self.rowmask, beta=self.beta if self.gamma2 is not None else None,
+                    gamma2=self.gamma2, stats2=self.stats2, ws2=self.ws2)
+
+    def fused(self):
+        global LN_BWD_FUSED_LAUNCHES
+        LN_BWD_FUSED_LAUNCHES += 1
+        self._launched()
 
 
 def _out_drop_grad(dy2, out_scale, p_out, s_out, rowmask=None):
@@ -964,39 +1032,27 @@ def _out_drop_grad(dy2, out_scale, p_out, s_out, rowmask=None):
         # the entry keeps the producing dx alive, so no other tensor can have been given this address meanwhile; an
         # in-place change of dx since (autograd summing a second consumer's gradient into it) shows in its version
         g, spec, dx, version = hit
-        pend = _PENDING_LN.get(g.data_ptr()) if _PENDING_LN else None
-        if dx._version != version or dx.numel() != dy2.numel():
-            if pend is not None:
-                _resolve_ln(_PENDING_LN.pop(g.data_ptr()))
-            return dropout_scale(dy2, out_scale, p_out, s_out, rowmask)
         same_mask = (spec[3] is None and rowmask is None) or (spec[3] is not None and rowmask is not None and
                                                                spec[3].data_ptr() == rowmask.data_ptr())
-        if spec[:3] == (float(out_scale), float(p_out), int(s_out)) and same_mask and g.numel() == dy2.numel():
+        if (dx._version == version and dx.numel() == dy2.numel() and spec[:3] == (float(out_scale), float(p_out), int(s_out)) and
+                same_mask and g.numel() == dy2.numel()):
             return g.view(dy2.shape)              # (possibly still parked: the caller's gemm_nn comes next and launches it)
+        pend = _PENDING_LN.take(g)
         if pend is not None:
-            _resolve_ln(_PENDING_LN.pop(g.data_ptr()))
+            pend.resolve()
     return dropout_scale(dy2, out_scale, p_out, s_out, rowmask)
 
 
 def _ln_bwd(dy, x, gamma, beta, act, stats, rows, d, rowmask, add, dx, dg, db, to_arena, prev_drop=None, fuse=False):
     ws = _ln_ws(x, rows, d)
-    g = None
     # (to_arena: the parameter gradients are written later than this function returns - fine for arena slices, which autograd never
     # sees, wrong for fresh tensors that PreNormFn.backward hands back to autograd right away)
-    if (fuse and to_arena and prev_drop is not None and LN_BWD_FUSE and FUSE_OUT_DROP and act == ACT_NONE and d == 256 and
-            hip.GEMM_PRECISION == 6 and rows >= ROWGEMM_MIN_ROWS and not _planes.active() and dy.is_contiguous() and x.is_contiguous() and
-            (add is None or add.is_contiguous())):
+    if (fuse and to_arena and prev_drop is not None and LN_BWD_FUSE and FUSE_OUT_DROP and act == ACT_NONE and _ln_rows_fusable(rows, d) and
+            dy.is_contiguous() and x.is_contiguous() and (add is None or add.is_contiguous())):
         # parked: the consuming block's first input-gradient GEMM launches it as its prologue (see _PENDING_LN)
         g = torch.empty_like(dx)
-        t = LN_TABLE
-        table = t is not None and to_arena
-        _PENDING_LN[g.data_ptr()] = dict(dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, add=add, dx=dx, g=g, ws=ws, spec=prev_drop,
-                                         rows=rows, d=d, dg=dg, db=db, table=table, done=False, rowmask=rowmask)
+        _PENDING_LN.park(_LnBwdPark(dy, x, gamma, beta, stats, add, dx, g, ws, prev_drop, rows, d, dg, db, rowmask=rowmask))
         _PREDROP[dx.data_ptr()] = (g, prev_drop, dx, dx._version)
-        if table:
-            t["entries"].append((ws.data_ptr(), rows, d, dg.data_ptr(), db.data_ptr()))
-            t["keep"].append(ws)
-            t["max_rows"], t["max_d"] = max(t["max_rows"], rows), max(t["max_d"], d)
         return
     if prev_drop is not None and FUSE_OUT_DROP and d % 8 == 0:
         g = torch.empty_like(dx)
@@ -1012,13 +1068,7 @@ def _ln_bwd(dy, x, gamma, beta, act, stats, rows, d, rowmask, add, dx, dg, db, t
         _PREDROP[dx.data_ptr()] = (g, prev_drop, dx, dx._version)
     else:
         hip.call("oe_layernorm_bwd_dx", dy, x, gamma, beta, act, stats, rows, d, rowmask, add, dx, ws)
-    t = LN_TABLE
-    if t is None or not to_arena:
-        hip.call("oe_layernorm_param_reduce", ws, rows, d, dg, db)
-        return
-    t["entries"].append((ws.data_ptr(), rows, d, dg.data_ptr(), db.data_ptr()))
-    t["keep"].append(ws)
-    t["max_rows"], t["max_d"] = max(t["max_rows"], rows), max(t["max_d"], d)
+    _ln_param_reduce(ws, rows, d, dg, db, to_arena)
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -1066,10 +1116,9 @@ class PreNormFn(torch.autograd.Function):
         rows = x.numel() // d
         y = torch.empty_like(x)
         stats = _new(rows, 2, like=x)
-        if (fuse_fwd and LN_FWD_FUSE and ROWGEMM and hip.GEMM_PRECISION == 6 and d == 256 and rows >= ROWGEMM_MIN_ROWS and not _planes.active() and
-                gamma.data_ptr() % 16 == 0 and beta.data_ptr() % 16 == 0):
+        if fuse_fwd and LN_FWD_FUSE and ROWGEMM and _ln_rows_fusable(rows, d) and gamma.data_ptr() % 16 == 0 and beta.data_ptr() % 16 == 0:
             # parked: the consumer's first kernel makes y (see _PENDING_LNF)
-            _PENDING_LNF[y.data_ptr()] = dict(x=x, gamma=gamma, beta=beta, eps=eps, rows=rows, d=d, rowmask=rowmask, y=y, stats=stats, done=False)
+            _PENDING_LNF.park(_LnFwdPark(x, gamma, beta, eps, rows, d, y, stats, rowmask=rowmask))
         else:
             _ln_fwd(x, gamma, beta, eps, rows, d, rowmask, ACT_NONE, y, stats)
         ctx.save_for_backward(x, gamma, beta, stats, rowmask)
@@ -1121,11 +1170,10 @@ class NormPairFn(torch.autograd.Function):
         u = torch.empty_like(x) if want_first else None
         y = torch.empty_like(x)
         st1, st2 = _new(rows, 2, like=x), _new(rows, 2, like=x)
-        if (fuse_fwd and want_first and LN_FWD_FUSE and FUSED_FFN and hip.GEMM_PRECISION == 6 and d == 256 and rows >= ROWGEMM_MIN_ROWS and
-                not _planes.active() and all(t.data_ptr() % 16 == 0 for t in (g1, b1, g2, b2))):
+        if (fuse_fwd and want_first and LN_FWD_FUSE and FUSED_FFN and _ln_rows_fusable(rows, d) and
+                all(t.data_ptr() % 16 == 0 for t in (g1, b1, g2, b2))):
             # parked: the next layer's first feed-forward makes u and y on its rows' way in (_PENDING_LNF, pair form)
-            _PENDING_LNF[y.data_ptr()] = dict(x=x, gamma=g1, beta=b1, eps=eps1, gamma2=g2, beta2=b2, eps2=eps2, rows=rows, d=d, rowmask=None,
-                                              u=u, y=y, stats=st1, stats2=st2, done=False)
+            _PENDING_LNF.park(_LnFwdPark(x, g1, b1, eps1, rows, d, y, st1, gamma2=g2, beta2=b2, eps2=eps2, u=u, stats2=st2))
         else:
             hip.call("oe_layernorm_pair_fwd", x, g1, b1, eps1, g2, b2, eps2, rows, d, u, st1, y, st2)
         ctx.save_for_backward(x, g1, b1, st1, g2, b2, st2)
@@ -1152,20 +1200,13 @@ class NormPairFn(torch.autograd.Function):
         ws1, ws2 = _ln_ws(x, rows, d), _ln_ws(x, rows, d)
         gout, alpha, p, seed, gmask = None, 1.0, 0.0, 0, None
         arena_all = rg1 is None and rb1 is None and rg2 is None and rb2 is None
-        if (ctx.ln_fuse and arena_all and ctx.prev_drop is not None and LN_BWD_FUSE and FUSE_OUT_DROP and d == 256 and hip.GEMM_PRECISION == 6 and
-                rows >= ROWGEMM_MIN_ROWS and not _planes.active() and x.is_contiguous() and (add is None or add.is_contiguous())):
+        if (ctx.ln_fuse and arena_all and ctx.prev_drop is not None and LN_BWD_FUSE and FUSE_OUT_DROP and _ln_rows_fusable(rows, d) and
+                x.is_contiguous() and (add is None or add.is_contiguous())):
             # parked: the previous block's backward (the second feed-forward's oe_ffn_bwd) launches it as its prologue (_PENDING_LN)
             gout = torch.empty_like(dx)
-            t = LN_TABLE
-            _PENDING_LN[gout.data_ptr()] = dict(dy=dy, x=x, gamma=g1, beta=b1, stats=st1, gamma2=g2, stats2=st2, add=add, dx=dx, g=gout, ws=ws1,
-                                                ws2=ws2, spec=ctx.prev_drop, rows=rows, d=d, dg=dg1, db=db1, dg2=dg2, db2=db2, table=t is not None,
-                                                done=False)
+            _PENDING_LN.park(_LnBwdPark(dy, x, g1, b1, st1, add, dx, gout, ws1, ctx.prev_drop, rows, d, dg1, db1,
+                                        gamma2=g2, stats2=st2, ws2=ws2, dg2=dg2, db2=db2))
             _PREDROP[dx.data_ptr()] = (gout, ctx.prev_drop, dx, dx._version)
-            if t is not None:
-                for ws, dg, db in ((ws1, dg1, db1), (ws2, dg2, db2)):
-                    t["entries"].append((ws.data_ptr(), rows, d, dg.data_ptr(), db.data_ptr()))
-                    t["keep"].append(ws)
-                t["max_rows"], t["max_d"] = max(t["max_rows"], rows), max(t["max_d"], d)
             return dx, rg1, rb1, None, rg2, rb2, None, None, None, None
         if ctx.prev_drop is not None and FUSE_OUT_DROP and d % 8 == 0:
             gout = torch.empty_like(dx)
@@ -1173,14 +1214,8 @@ class NormPairFn(torch.autograd.Function):
         hip.call("oe_layernorm_pair_bwd_dx_drop", dy, x, g1, b1, st1, g2, st2, rows, d, add, dx, gout, alpha, p, seed, _seed_dev, gmask, ws1, ws2)
         if gout is not None:
             _PREDROP[dx.data_ptr()] = (gout, ctx.prev_drop, dx, dx._version)
-        t = LN_TABLE
-        for ws, dg, db, to_arena in ((ws1, dg1, db1, rg1 is None and rb1 is None), (ws2, dg2, db2, rg2 is None and rb2 is None)):
-            if t is None or not to_arena:
-                hip.call("oe_layernorm_param_reduce", ws, rows, d, dg, db)
-            else:
-                t["entries"].append((ws.data_ptr(), rows, d, dg.data_ptr(), db.data_ptr()))
-                t["keep"].append(ws)
-                t["max_rows"], t["max_d"] = max(t["max_rows"], rows), max(t["max_d"], d)
+        _ln_param_reduce(ws1, rows, d, dg1, db1, rg1 is None and rb1 is None)
+        _ln_param_reduce(ws2, rows, d, dg2, db2, rg2 is None and rb2 is None)
         return dx, rg1, rb1, None, rg2, rb2, None, None, None, None
 
 
@@ -1359,6 +1394,11 @@ def _ffn_bwd_fused() -> bool:
     return (hip.GEMM_PRECISION == 6) if FUSED_FFN_BWD is None else bool(FUSED_FFN_BWD)
 
 
+def _ffn6_takes_ln(d, ff):
+    """The fused feed-forward's kernel (csrc/ffn6.hip) has the LayerNorm prologues (oe_ffn_fwd's lnf, oe_ffn_bwd's ln)."""
+    return hip.GEMM_PRECISION == 6 and d == 256 and ff % 256 == 0 and hip.lib().oe_ffn6_config(-1) in (0, 3)
+
+
 def _ffn_fused_ok(x2, w1, w2, act, res2):
     d, ff = w1.shape[1], w1.shape[0]
     if hip.GEMM_PRECISION == 0 or x2.shape[0] < FUSED_FFN_MIN_ROWS or not hip.lib().oe_ffn_supported(d, ff, hip.GEMM_PRECISION, act):
@@ -1462,20 +1502,15 @@ class FeedForwardFn(torch.autograd.Function):
         M, ff = x2.shape[0], w1.shape[0]
         s_in, s_out = (next_seed() if p_in > 0 else 0), (next_seed() if p_out > 0 else 0)
         res2 = None if residual is None else _chk(residual, "residual").reshape(-1, w2.shape[0])
-        lnf_p = _lnf_take(x2)                     # x may be the output of a parked LayerNorm forward (_PENDING_LNF)
+        lnf_p = _PENDING_LNF.take(x2)             # x may be the output of a parked LayerNorm forward (_PENDING_LNF)
         fused_now = FUSED_FFN and _ffn_fused_ok(x2, w1, w2, act, res2)
         lnf = None
-        if lnf_p is not None:
-            if (fused_now and hip.GEMM_PRECISION == 6 and d == 256 and ff % 256 == 0 and hip.lib().oe_ffn6_config(-1) in (0, 3) and
-                    x2.is_contiguous() and M == lnf_p["rows"]):
-                lnf = dict(x=lnf_p["x"], gamma=lnf_p["gamma"], beta=lnf_p["beta"], eps=lnf_p["eps"], y=lnf_p["y"], stats=lnf_p["stats"],
-                           rowmask=lnf_p["rowmask"], gamma2=lnf_p.get("gamma2"), beta2=lnf_p.get("beta2"), eps2=lnf_p.get("eps2"),
-                           u=lnf_p.get("u"), stats2=lnf_p.get("stats2"))
-                if lnf["gamma2"] is not None and (res2 is None or lnf["u"] is None or res2.data_ptr() != lnf["u"].data_ptr()):
-                    lnf = None                    # the pair form is for `residual = u` (EncoderLayer's pre): anything else, the plain way
-                    _resolve_lnf(lnf_p)
+        if lnf_p is not None:                     # (the pair form is for `residual = u` (EncoderLayer's pre): anything else, the plain way)
+            if (fused_now and _ffn6_takes_ln(d, ff) and x2.is_contiguous() and M == lnf_p.rows and
+                    (lnf_p.gamma2 is None or (res2 is not None and lnf_p.u is not None and res2.data_ptr() == lnf_p.u.data_ptr()))):
+                lnf = lnf_p.prologue()
             else:
-                _resolve_lnf(lnf_p)
+                lnf_p.resolve()
         if fused_now:
             # one kernel (csrc/ffn.hip): the (M, ff) intermediate stays in registers; pre / a are written only when a
             # backward will read them
@@ -1487,19 +1522,17 @@ class FeedForwardFn(torch.autograd.Function):
             hip.ffn_fwd(x2, w1p, b1, w2p, b2, M, d, ff, act, drop_in=p_in, seed_in=s_in, drop_out=p_out, seed_out=s_out,
                         seed_dev=_seed_dev, pre_out=pre, act_out=a, residual=res2, ldr=0 if res2 is None else res2.stride(0),
                         beta=out_scale, y=y, lnf=lnf)
-            global LN_FWD_FUSED_LAUNCHES, FFN_FWD_FUSED_LAUNCHES
+            global FFN_FWD_FUSED_LAUNCHES
             FFN_FWD_FUSED_LAUNCHES += 1
             if lnf is not None:
-                lnf_p["done"] = True
-                LN_FWD_FUSED_LAUNCHES += 1
+                lnf_p.fused()
             ctx.save_for_backward(x2, w1, w2, pre, a)
             ctx.biases = (b1, b2)
             ctx.cfg = (act, p_in, s_in, out_scale, p_out, s_out, residual is not None, x.shape)
             ctx.fused = True
             # (the backward's fused kernel can take the next LayerNorm's backward as its prologue: _PENDING_LN)
-            lnf = (LN_BWD_FUSE and FUSE_OUT_DROP and hip.GEMM_PRECISION == 6 and d == 256 and M >= ROWGEMM_MIN_ROWS and ff % 256 == 0 and
-                   _ffn_bwd_fused() and hip.lib().oe_ffn6_config(-1) in (0, 3) and not _planes.active())
-            return _tag_out_drop(y.view(*x.shape[:-1], w2.shape[0]), out_scale, p_out, s_out, ln_fuse=lnf)
+            ln_fuse = LN_BWD_FUSE and FUSE_OUT_DROP and _ln_rows_fusable(M, d) and _ffn_bwd_fused() and _ffn6_takes_ln(d, ff)
+            return _tag_out_drop(y.view(*x.shape[:-1], w2.shape[0]), out_scale, p_out, s_out, ln_fuse=ln_fuse)
         ctx.fused = False
         pre = _new(M, ff, like=x)
         if act in GEMM_FUSED_ACTS:
@@ -1525,34 +1558,29 @@ class FeedForwardFn(torch.autograd.Function):
         dy2 = dy.view(-1, w2.shape[0])
         g2 = dy2 if (p_out == 0 and out_scale == 1.0) else _out_drop_grad(dy2, out_scale, p_out, s_out)
         b1, b2 = ctx.biases
-        pend = _PENDING_LN.pop(g2.data_ptr(), None) if _PENDING_LN else None     # g2 may be a parked LayerNorm backward
+        pend = _PENDING_LN.take(g2)               # g2 may be a parked LayerNorm backward
         if ctx.fused and _ffn_bwd_fused() and g2.stride(0) % 4 == 0:
             # both input-gradient GEMMs in one launch (csrc/ffn.hip, oe_ffn_bwd): dH is written once and never re-read here
             M, d, ff = g2.shape[0], w2.shape[0], w1.shape[0]
-            prec = hip.GEMM_PRECISION
-            nbytes = hip.lib().oe_ffn_packed_bytes(d, ff, prec)
             w2tp, w1tp = _ffn_packed(w1, w2, d, ff, bwd=True)
             dh, dx = _new(M, ff, like=g2), _new(M, d, like=g2)
             ln = None
-            if pend is not None and not pend.get("done"):
-                if (prec == 6 and d == 256 and ff % 256 == 0 and hip.lib().oe_ffn6_config(-1) in (0, 3) and g2.is_contiguous() and
-                        g2.data_ptr() == pend["g"].data_ptr() and M == pend["rows"]):
-                    ln = _ln_dict(pend)
+            if pend is not None and not pend.done:
+                if _ffn6_takes_ln(d, ff) and g2.is_contiguous() and g2.data_ptr() == pend.g.data_ptr() and M == pend.rows:
+                    ln = pend.prologue()
                 else:
-                    _resolve_ln(pend)
+                    pend.resolve()
             # FIRST launch of this backward: it makes g2 when that is a parked LayerNorm backward (the weight gradient reads it after)
             hip.ffn_bwd(g2, w2tp, w1tp, M, d, ff, act, drop_in=p_in, seed_in=s_in, seed_dev=_seed_dev, pre=pre, dh=dh, dx=dx, ln=ln)
-            global LN_BWD_FUSED_LAUNCHES, FFN_BWD_FUSED_LAUNCHES
+            global FFN_BWD_FUSED_LAUNCHES
             FFN_BWD_FUSED_LAUNCHES += 1
             if ln is not None:
-                pend["done"] = True
-                LN_BWD_FUSED_LAUNCHES += 1
-                _ln_reduce(pend)
+                pend.fused()
             dw2, db2 = wgrad_bias(w2, b2, g2, a)
             dw1, db1 = wgrad_bias(w1, b1, dh, x2)
             return dx.view(in_shape), dw1, db1, dw2, db2, None, None, (dy if has_res else None), None, None
         if pend is not None:
-            _resolve_ln(pend)
+            pend.resolve()
         dw2, db2 = wgrad_bias(w2, b2, g2, a)
         if act in GEMM_FUSED_ACTS:
             dh = gemm_nn(g2, w2, act=act, actgrad_in=pre, ld_aux=pre.stride(0), drop_p=p_in, seed=s_in, seed_dev=_seed_dev, out_planes=True)
@@ -1883,21 +1911,14 @@ class ConvModuleFn(torch.autograd.Function):
         # the norm + activation behind the depthwise convolution: its backward as the EPILOGUE of pointwise_conv2's input gradient
         # (oe_rowgemm6's lne arguments: the block owns whole rows), when that launch is the 256 <- 256 row-block kernel
         epi_ln = None
-        if (LN_EPI_FUSE and ROWGEMM and hip.GEMM_PRECISION == 6 and d == 256 and B * T >= ROWGEMM_MIN_ROWS and act in GEMM_FUSED_ACTS and
-                not _planes.active() and to_arena):
+        if LN_EPI_FUSE and ROWGEMM and _ln_rows_fusable(B * T, d) and act in GEMM_FUSED_ACTS and to_arena:
             epi_ln = dict(x=yc, stats=stats, gamma=g, beta=b, act=act, dx=dyc, ws=_ln_ws(yc, B * T, d), done=False)
         dz = gemm_nn(gq, w2m, ln_epi=epi_ln)     # FIRST: gq may be a parked LayerNorm backward that this launch makes (_PENDING_LN)
         dw2, db2 = wgrad_bias(w2, b2, gq, z)
         if epi_ln is not None and epi_ln["done"]:
             global LN_EPI_FUSED_LAUNCHES
             LN_EPI_FUSED_LAUNCHES += 1
-            t = LN_TABLE
-            if t is None:
-                hip.call("oe_layernorm_param_reduce", epi_ln["ws"], B * T, d, dg, dbeta)
-            else:
-                t["entries"].append((epi_ln["ws"].data_ptr(), B * T, d, dg.data_ptr(), dbeta.data_ptr()))
-                t["keep"].append(epi_ln["ws"])
-                t["max_rows"], t["max_d"] = max(t["max_rows"], B * T), max(t["max_d"], d)
+            _ln_param_reduce(epi_ln["ws"], B * T, d, dg, dbeta, to_arena)
         else:
             _ln_bwd(dz, yc, g, b, act, stats, B * T, d, None, None, dyc, dg, dbeta, to_arena)
         da = torch.empty_like(a)

@@ -329,12 +329,12 @@ def test_ln_backward_prologue_equals_the_two_launches(rows, p, with_add, with_ma
             # one launch
             dx1, g1, ws1 = torch.full_like(x, float("nan")), torch.full_like(x, float("nan")), torch.zeros(nws, device=DEV)
             dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
-            pend = dict(dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, add=add, dx=dx1, g=g1, ws=ws1, spec=(0.5, p, 0x1234, gmask), rows=rows, d=d,
-                        dg=dg, db=db, table=False, done=False, rowmask=lmask)
-            ops._PENDING_LN[g1.data_ptr()] = pend
+            pend = ops._LnBwdPark(dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, add=add, dx=dx1, g=g1, ws=ws1, spec=(0.5, p, 0x1234, gmask),
+                                  rows=rows, d=d, dg=dg, db=db, rowmask=lmask)
+            ops._PENDING_LN.park(pend)
             n0 = ops.LN_BWD_FUSED_LAUNCHES
             y1 = ops.gemm_nn(g1, w)
-            assert ops.LN_BWD_FUSED_LAUNCHES == n0 + 1 and pend["done"] and not ops._PENDING_LN
+            assert ops.LN_BWD_FUSED_LAUNCHES == n0 + 1 and pend.done and not ops._PENDING_LN
     finally:
         ops._seed_dev = old
     dg0, db0 = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
@@ -361,9 +361,9 @@ def test_a_parked_layernorm_backward_is_resolved_on_every_other_path():
 
     def park():
         dx, g = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
-        pend = dict(dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, add=None, dx=dx, g=g, ws=torch.zeros(nws, device=DEV), spec=(1.0, 0.0, 0, None),
-                    rows=rows, d=d, dg=torch.zeros(d, device=DEV), db=torch.zeros(d, device=DEV), table=False, done=False)
-        ops._PENDING_LN[g.data_ptr()] = pend
+        pend = ops._LnBwdPark(dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, add=None, dx=dx, g=g, ws=torch.zeros(nws, device=DEV),
+                              spec=(1.0, 0.0, 0, None), rows=rows, d=d, dg=torch.zeros(d, device=DEV), db=torch.zeros(d, device=DEV))
+        ops._PENDING_LN.park(pend)
         return pend
 
     want = torch.empty_like(x)
@@ -372,14 +372,14 @@ def test_a_parked_layernorm_backward_is_resolved_on_every_other_path():
         w_wide = torch.nn.Parameter(torch.randn(256, 320, device=DEV) / 16)            # output 320 wide (not a multiple of 128): oe_gemm_f32
         pend = park()
         n0 = ops.LN_BWD_FUSED_LAUNCHES
-        y = ops.gemm_nn(pend["g"], w_wide)
-        assert pend["done"] and ops.LN_BWD_FUSED_LAUNCHES == n0 and not ops._PENDING_LN
+        y = ops.gemm_nn(pend.g, w_wide)
+        assert pend.done and ops.LN_BWD_FUSED_LAUNCHES == n0 and not ops._PENDING_LN
         torch.cuda.synchronize()
-        assert torch.equal(pend["dx"], want) and torch.equal(pend["g"], want) and bool(torch.isfinite(y).all())      # (the same kernel: exact)
+        assert torch.equal(pend.dx, want) and torch.equal(pend.g, want) and bool(torch.isfinite(y).all())      # (the same kernel: exact)
         pend = park()
-        assert ops.resolve_pending_ln() == 1 and pend["done"] and not ops._PENDING_LN
+        assert ops.resolve_pending_ln() == 1 and pend.done and not ops._PENDING_LN
         torch.cuda.synchronize()
-        assert torch.equal(pend["dx"], want)
+        assert torch.equal(pend.dx, want)
 
 
 @pytest.mark.parametrize("rows,n,with_mask", [(7936, 768, False), (4099, 512, True)])
@@ -398,14 +398,14 @@ def test_ln_forward_prologue_equals_the_two_launches(rows, n, with_mask):
     with torch.no_grad():
         out0 = ops.gemm_nt(y0, w, b)
         y1, st1 = torch.full_like(x, float("nan")), torch.full((rows, 2), float("nan"), device=DEV)
-        pend = dict(x=x, gamma=gamma, beta=beta, eps=1e-5, rows=rows, d=d, rowmask=mask, y=y1, stats=st1, done=False)
-        ops._PENDING_LNF[y1.data_ptr()] = pend
+        pend = ops._LnFwdPark(x=x, gamma=gamma, beta=beta, eps=1e-5, rows=rows, d=d, rowmask=mask, y=y1, stats=st1)
+        ops._PENDING_LNF.park(pend)
         n0 = ops.LN_FWD_FUSED_LAUNCHES
         out1 = ops.gemm_nt(y1, w, b)
-        assert ops.LN_FWD_FUSED_LAUNCHES == n0 + 1 and pend["done"] and not ops._PENDING_LNF
+        assert ops.LN_FWD_FUSED_LAUNCHES == n0 + 1 and pend.done and not ops._PENDING_LNF
         # any other op of the module that receives a parked tensor launches the LayerNorm on its own first
         y2, st2 = torch.full_like(x, float("nan")), torch.full((rows, 2), float("nan"), device=DEV)
-        ops._PENDING_LNF[y2.data_ptr()] = dict(x=x, gamma=gamma, beta=beta, eps=1e-5, rows=rows, d=d, rowmask=mask, y=y2, stats=st2, done=False)
+        ops._PENDING_LNF.park(ops._LnFwdPark(x=x, gamma=gamma, beta=beta, eps=1e-5, rows=rows, d=d, rowmask=mask, y=y2, stats=st2))
         z = ops.add(y2, y2) if hasattr(ops, "add") else None
     torch.cuda.synchronize()
     torch.testing.assert_close(y1, y0, rtol=2e-6, atol=1e-6)

@@ -349,3 +349,90 @@ def test_pack_table_dead_row_predicates():
     ftab.sweep(ops._ffn_dead)
     assert set(ftab.entries) == {fkeys["untouched"]}
     assert [int(ftab.host[i, 0]) for i in range(ftab.n)] == [0, 0, fkeys["untouched"][0]]
+
+
+def test_parked_layernorm_entries_and_reduce_table(monkeypatch):
+    """ops._LnFwdPark / _LnBwdPark / _ParkRegistry / _ln_param_reduce (host logic only, hip.call recorded): resolve() of a single
+    and a pair entry, forward and backward, issues exactly the separate launches - names and argument order - and nothing the second
+    time; a backward parked in table mode records its rows at once and reduces nothing when launched; sweep() launches what is not
+    done and empties the registry; a parameter-gradient reduce is a table row in table mode (arena gradients only), else a launch."""
+    from openeat_amd import hip, ops, planes
+    calls = []
+    monkeypatch.setattr(hip, "call", lambda name, *args: calls.append((name,) + args))
+    monkeypatch.setattr(planes, "POLICY", "conv")                  # (no pre-split operands: the plain LayerNorm forward)
+    monkeypatch.setattr(ops, "_seed_dev", torch.zeros(1, dtype=torch.int64))
+    monkeypatch.setattr(ops, "LN_TABLE", None)
+    sd = ops._seed_dev
+
+    def expect(*want):
+        got = calls[:]
+        calls.clear()
+        same = lambda a, b: a is b if any(v is None or isinstance(v, torch.Tensor) for v in (a, b)) else a == b
+        assert len(got) == len(want), got
+        for c, w in zip(got, want):
+            assert c[0] == w[0] and len(c) == len(w) and all(same(a, b) for a, b in zip(c[1:], w[1:])), (c[0], w[0])
+
+    rows, d = 6, 8
+    x, dy, add, u, y, g, dx = (torch.zeros(rows, d) for _ in range(7))
+    g1, b1, g2, b2, dg1, db1, dg2, db2 = (torch.zeros(d) for _ in range(8))
+    st1, st2, mask, gmask, ws1, ws2 = torch.zeros(rows, 2), torch.zeros(rows, 2), torch.ones(rows), torch.ones(rows), torch.zeros(64), torch.zeros(64)
+    spec = (0.5, 0.1, 1234, gmask)
+
+    single = ops._LnFwdPark(x, g1, b1, 1e-5, rows, d, y, st1, rowmask=mask)
+    pair = ops._LnFwdPark(x, g1, b1, 1e-5, rows, d, y, st1, gamma2=g2, beta2=b2, eps2=1e-6, u=u, stats2=st2)
+    for e in (single, single, pair, pair):
+        e.resolve()
+    expect(("oe_layernorm_fwd", x, g1, b1, 1e-5, rows, d, mask, 0, y, st1),
+           ("oe_layernorm_pair_fwd", x, g1, b1, 1e-5, g2, b2, 1e-6, rows, d, u, st1, y, st2))
+    assert single.done and pair.done
+
+    def bwd(g_=g, pair_=False):
+        if pair_:
+            return ops._LnBwdPark(dy, x, g1, b1, st1, add, dx, g_, ws1, spec, rows, d, dg1, db1, gamma2=g2, stats2=st2, ws2=ws2, dg2=dg2, db2=db2)
+        return ops._LnBwdPark(dy, x, g1, b1, st1, add, dx, g_, ws1, spec, rows, d, dg1, db1, rowmask=mask)
+
+    single, pair = bwd(), bwd(pair_=True)
+    for e in (single, single, pair, pair):
+        e.resolve()
+    expect(("oe_layernorm_bwd_dx_drop", dy, x, g1, b1, 0, st1, rows, d, mask, add, dx, g, 0.5, 0.1, 1234, sd, gmask, ws1),
+           ("oe_layernorm_param_reduce", ws1, rows, d, dg1, db1),
+           ("oe_layernorm_pair_bwd_dx_drop", dy, x, g1, b1, st1, g2, st2, rows, d, add, dx, g, 0.5, 0.1, 1234, sd, gmask, ws1, ws2),
+           ("oe_layernorm_param_reduce", ws1, rows, d, dg1, db1), ("oe_layernorm_param_reduce", ws2, rows, d, dg2, db2))
+    n0 = ops.LN_BWD_FUSED_LAUNCHES
+    bwd(pair_=True).fused()
+    expect(("oe_layernorm_param_reduce", ws1, rows, d, dg1, db1), ("oe_layernorm_param_reduce", ws2, rows, d, dg2, db2))
+    assert ops.LN_BWD_FUSED_LAUNCHES == n0 + 1
+
+    # table mode: the rows go in when the entry is parked, whatever happens later
+    table = ops._LnTable(torch.zeros(8, 5, dtype=torch.int64), eager=False)
+    monkeypatch.setattr(ops, "LN_TABLE", table)
+    parked = bwd(pair_=True)
+    assert table.entries == [(ws1.data_ptr(), rows, d, dg1.data_ptr(), db1.data_ptr()), (ws2.data_ptr(), rows, d, dg2.data_ptr(), db2.data_ptr())]
+    assert table.keep == [ws1, ws2] and (table.max_rows, table.max_d) == (rows, d)
+    parked.resolve()
+    parked.fused()
+    expect(("oe_layernorm_pair_bwd_dx_drop", dy, x, g1, b1, st1, g2, st2, rows, d, add, dx, g, 0.5, 0.1, 1234, sd, gmask, ws1, ws2))
+    ops._ln_param_reduce(ws1, 2 * rows, 2 * d, dg1, db1, True)
+    assert len(table.entries) == 3 and table.keep[-1] is ws1 and (table.max_rows, table.max_d) == (2 * rows, 2 * d)
+    expect()
+    ops._ln_param_reduce(ws1, rows, d, dg1, db1, False)
+    monkeypatch.setattr(ops, "LN_TABLE", None)
+    ops._ln_param_reduce(ws2, rows, d, dg2, db2, True)
+    expect(("oe_layernorm_param_reduce", ws1, rows, d, dg1, db1), ("oe_layernorm_param_reduce", ws2, rows, d, dg2, db2))
+    assert len(table.entries) == 3
+
+    # the registry: keyed by the parked output, take() removes, sweep() launches what nobody launched
+    reg = ops._ParkRegistry("g")
+    monkeypatch.setattr(ops, "_PENDING_LN", reg)
+    gs = [torch.zeros(rows, d) for _ in range(4)]
+    entries = [bwd(g_) for g_ in gs]
+    for e in entries:
+        reg.park(e)
+    assert len(reg) == 4 and reg.take(torch.zeros(rows, d)) is None and reg.take(gs[0]) is entries[0] and reg.take(gs[0]) is None
+    entries[1].resolve()
+    calls.clear()
+    assert ops.resolve_pending_ln() == 2 and not reg and reg.take(gs[2]) is None
+    assert [c[0] for c in calls] == ["oe_layernorm_bwd_dx_drop", "oe_layernorm_param_reduce"] * 2
+    assert calls[0][12] is gs[2] and calls[2][12] is gs[3]
+    calls.clear()
+    assert reg.sweep() == 0 and not calls and not entries[0].done
