@@ -398,6 +398,29 @@ int oe_ctc_loss_fused(const float* logits, long ldv, int B, int T, int V, const 
 int oe_ctc_greedy(const float* logits, long ldv, int B, int T, int V, const int* hlens, int eos,
                   int* frame_best, int* out_tokens, int* out_lens, void* stream);
 
+/* CTC forced alignment on device: the best path through the trellis the loss sums over (ctc.py:27-45: blank, y1, blank, ..
+ * blank; blank = 0) - token times and confidences.  The reference has no aligner (WeNet, which it derives from, has one);
+ * these are the semantics every layer refers to.  With Tb = hlens[b], y = targets[b, :tlens[b]] (L labels),
+ * lp = log_softmax(logits[b, t, :V]) in natural log and ext[s] = (s odd ? y[s >> 1] : 0), s = 0 .. 2L:
+ *   v[0,0] = lp[0,0], v[0,1] = lp[0,ext[1]], every other state of frame 0 is -inf;
+ *   v[t,s] = lp[t,ext[s]] + max(v[t-1,s], v[t-1,s-1], v[t-1,s-2]), the third term only for odd s >= 3 with ext[s] != ext[s-2];
+ *   the path ends in state 2L or 2L-1, whichever has the larger v[Tb-1, .].
+ *   Ties: a predecessor replaces the best only if strictly greater, tried in the order stay (s), step (s-1), skip (s-2);
+ *   at the end 2L is kept unless 2L-1 is strictly greater.
+ *   out: frames (B, T) int32 = ext[state_t] for t < Tb, -1 for t >= Tb;  tok_start / tok_end (B, Lmax) int32 = first / last
+ *        frame (inclusive) spent in state 2l+1, -1 for l >= L;  tok_logp (B, Lmax) = sum of lp[t, y[l]] over those frames,
+ *        0 for l >= L;  score (B) = v[Tb-1, final].  tok_start, tok_end, tok_logp may each be NULL.
+ *   Infeasible utterances (Tb == 0, or fewer frames than L + adjacent repeats - what the loss calls infeasible): score -inf,
+ *        frames / tok_start / tok_end all -1, tok_logp 0.  An empty target with Tb > 0 is feasible: every frame blank.
+ *   logits, hlens, targets, tlens as oe_ctc_loss_fused (read only);  Lmax <= 255;
+ *   workspace: oe_ctc_align_workspace_bytes(B,T,Lmax) bytes, 16-byte aligned.
+ * Two launches (the loss's row pass, then one wave per utterance: recursion and back-trace); no allocation, no
+ * synchronisation, no host-side state: capturable. */
+size_t oe_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int oe_ctc_align(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets, int Lmax,
+                 const int* tlens, int* frames, int* tok_start, int* tok_end, float* tok_logp, float* score, void* workspace,
+                 void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

@@ -19,6 +19,7 @@
 //                 utterances are zeroed (zero_infinity)
 // Algorithmic bytes: 2*B*T*V*4 (+ 3 small state arrays), which is what k1 moves.
 #include <stdlib.h>
+#include <type_traits>
 #include "oe_common.h"
 #include "../../include/openeat_hip.h"
 
@@ -912,5 +913,252 @@ extern "C" int oe_ctc_greedy(const float* logits, long ldv, int B, int T, int V,
     OE_LAUNCH_CHECK("argmax_rows");
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(B), dim3(64), 0, st, frame_best, T, hlens, eos, out_tokens, out_lens);
     OE_LAUNCH_CHECK("ctc_collapse");
+    return 0;
+}
+
+// ------------------------------------------------------- forced alignment ----
+// The max-product twin of the alpha recursion: the best path through the trellis of ctc.py:27-45 (blank, y1, blank, .. blank;
+// skip between different labels only) instead of the sum over all of them.  The reference has no aligner; the semantics
+// (tie rule included) are in include/openeat_hip.h.
+//   launch 1: ctc_rows_kernel<NV4, false>, exactly as the loss-only path: lp[b,t,s] = log2-prob at the 2L+1 states
+//   launch 2: ctc_align_kernel, one wave per utterance:
+//     recursion  v[t,s] = lp[t,s] + max(stay, step, skip), states NS per lane, neighbours by the DPP shifts, lp prefetched a
+//                chunk ahead - ctc_recurse<true> with max for the log-sum-exp.  Each step also leaves one word per lane: the
+//                moves of its NS states, 2 bits each (0 stay / 1 step / 2 skip).  A lane only ever reads back its own words,
+//                so they are private storage and need no fence: in LDS (one byte per lane and frame for NS <= 4, two for
+//                NS = 8) while T * 64 of them fit CTC_ALIGN_LDS = 60 KiB - the 64 KiB a launch may ask for without a
+//                per-function opt-in, less the span table - i.e. T <= 960 (Sp <= 256) or T <= 480 (Sp <= 512); in the
+//                workspace for longer batches (the route depends on T and Sp only, not on the data).
+//     back-trace the whole wave walks from Tb-1 to 0 with the state in a scalar register: every lane loads its word of a
+//                frame (addresses do not depend on the path: 16 frames in flight), v_readlane picks the current state's, so
+//                a step of the chain is a readlane, a shift and a subtract.  Lane t & 63 keeps (state, move) of frame t;
+//                after 64 frames the wave writes that tile of `frames` and marks the spans' first / last frames in LDS.
+//     spans      one lane per label: start, end, and the sum of lp over the span (a fixed order: deterministic).
+// Bound: a latency chain of Tb dependent steps on one wave, like alphabeta; the back-trace adds a shorter chain of Tb.
+#define CTC_ALIGN_LDS (60 * 1024)
+#define CTC_ALIGN_PF 16          // frames of back-pointers in flight during the back-trace
+
+template <int NS, int CH, bool FULL, typename BPT>
+__device__ __forceinline__ void ctc_align_chunk(int c0, int Tb, float (&a)[NS], const float (&cap)[NS], const float (&cur)[CH][NS], BPT* bpl) {
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        if (FULL || c0 + i < Tb) {       // wave-uniform; whole chunks carry no test
+            const float p1 = wave_shr1(a[NS - 1]);
+            const float p2 = NS >= 2 ? wave_shr1(a[NS >= 2 ? NS - 2 : 0]) : wave_shr1(p1);
+            float na[NS];
+            unsigned w = 0;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const float n1 = (j >= 1) ? a[j >= 1 ? j - 1 : 0] : p1;
+                const float n2 = fminf((j >= 2) ? a[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2), cap[j]);
+                // a predecessor replaces the best only if strictly greater, in the order stay, step, skip
+                float best = a[j];
+                unsigned mv = 0;
+                if (n1 > best) { best = n1; mv = 1; }
+                if (n2 > best) { best = n2; mv = 2; }
+                na[j] = best + cur[i][j];
+                w |= mv << (2 * j);
+            }
+#pragma unroll
+            for (int j = 0; j < NS; ++j) a[j] = na[j];
+            bpl[(size_t)(c0 + i) * 64] = (BPT)w;
+        }
+    }
+}
+
+// bpl: this lane's column of the back-pointer words, word of frame t at bpl[t * 64] (LDS or workspace)
+template <int NS, int CH, typename BPT>
+__device__ __forceinline__ void ctc_align_wave(BPT* bpl, int* __restrict__ span, int b, int T, int Tb, int L, int Lmax, int Sp,
+                                               const int* __restrict__ tg, const float* __restrict__ lp_rows, int* __restrict__ frames,
+                                               int* __restrict__ tok_start, int* __restrict__ tok_end, float* __restrict__ tok_logp,
+                                               float* __restrict__ score) {
+    const int lane = threadIdx.x;
+    const int S = 2 * L + 1;
+    const int s0 = lane * NS;
+    int* fr = frames + (long)b * T;
+    float sc = NEG_INF;
+    bool feasible = false;
+    for (int l = lane; l < 2 * Lmax; l += 64) span[l] = -1;            // [0, Lmax): first frames, [Lmax, 2 Lmax): last frames
+    if (Tb > 0) {
+        // ---- recursion (see ctc_recurse: finite "log 0", states past S carry lp = 0 and never feed a valid state)
+        float cap[NS], a[NS];
+        bool valid[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int s = s0 + j;
+            valid[j] = s < S;
+            const bool skip = s < S && (s & 1) && s >= 3 && tg[s >> 1] != tg[(s - 2) >> 1];
+            cap[j] = skip ? 3.0e38f : CTC_NEG;
+        }
+        const float* lp0 = lp_rows + s0;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            a[j] = CTC_NEG;
+            if (valid[j] && s0 + j <= 1) a[j] = lp0[j];
+        }
+        float cur[CH][NS], nxt[CH][NS];
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                cur[i][j] = 0.f;
+                if (1 + i < Tb && valid[j]) cur[i][j] = lp0[(long)(1 + i) * Sp + j];
+            }
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) asm volatile("" : "+v"(cur[i][j]));
+        for (int c0 = 1; c0 < Tb; c0 += CH) {
+#pragma unroll
+            for (int i = 0; i < CH; ++i)
+#pragma unroll
+                for (int j = 0; j < NS; ++j) {
+                    nxt[i][j] = 0.f;
+                    if (c0 + CH + i < Tb && valid[j]) nxt[i][j] = lp0[(long)(c0 + CH + i) * Sp + j];
+                }
+            if (c0 + CH <= Tb) ctc_align_chunk<NS, CH, true>(c0, Tb, a, cap, cur, bpl);
+            else ctc_align_chunk<NS, CH, false>(c0, Tb, a, cap, cur, bpl);
+            // the next chunk becomes current here, one wait per chunk (see ctc_recurse)
+#pragma unroll
+            for (int i = 0; i < CH; ++i)
+#pragma unroll
+                for (int j = 0; j < NS; ++j) {
+                    cur[i][j] = nxt[i][j];
+                    asm volatile("" : "+v"(cur[i][j]));
+                }
+        }
+        // ---- end state: 2L unless 2L-1 is strictly greater
+        float e0 = CTC_NEG, e1 = CTC_NEG;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            if (s0 + j == S - 1) e0 = a[j];
+            if (s0 + j == S - 2) e1 = a[j];
+        }
+        e0 = wave_max(e0);
+        e1 = wave_max(e1);
+        const float best = (e1 > e0) ? e1 : e0;
+        feasible = best > 0.5f * CTC_NEG;
+        if (feasible) {
+            sc = best * CTC_LN2;
+            // ---- back-trace
+            int s = __builtin_amdgcn_readfirstlane((e1 > e0) ? S - 2 : S - 1);
+            int above = -1;                                  // state of the frame after the tile in hand
+            for (int t0 = (Tb - 1) & ~63; t0 >= 0; t0 -= 64) {
+                const int thi = min(Tb - 1, t0 + 63);
+                int myS = -1, myMv = 0;
+                for (int g = thi; g >= t0; g -= CTC_ALIGN_PF) {
+                    unsigned w[CTC_ALIGN_PF];
+#pragma unroll
+                    for (int k = 0; k < CTC_ALIGN_PF; ++k) {
+                        const int t = g - k;
+                        w[k] = 0u;
+                        if (t >= t0 && t >= 1) w[k] = bpl[(size_t)t * 64];
+                    }
+#pragma unroll
+                    for (int k = 0; k < CTC_ALIGN_PF; ++k) {
+                        const int t = g - k;
+                        if (t >= t0) {                       // wave-uniform
+                            const int mv = (__builtin_amdgcn_readlane((int)w[k], (unsigned)s / NS) >> (2 * ((unsigned)s % NS))) & 3;      // 0 at t = 0
+                            if (lane == (t & 63)) { myS = s; myMv = mv; }
+                            s = max(s - mv, 0);
+                        }
+                    }
+                }
+                const int t = t0 + lane;
+                const int up = __shfl_down(myS, 1, 64);
+                if (t <= thi) {
+                    fr[t] = (myS & 1) ? tg[myS >> 1] : 0;
+                    if (myS & 1) {
+                        if (myMv != 0 || t == 0) span[myS >> 1] = t;
+                        if ((t == thi ? above : up) != myS) span[Lmax + (myS >> 1)] = t;
+                    }
+                }
+                above = __builtin_amdgcn_readfirstlane(myS);
+            }
+        }
+    }
+    for (int t = (feasible ? Tb : 0) + lane; t < T; t += 64) fr[t] = -1;
+    if (lane == 0) score[b] = sc;
+    __syncthreads();
+    // ---- spans: one lane per label
+    for (int l = lane; l < Lmax; l += 64) {
+        const int st = (feasible && l < L) ? span[l] : -1, en = (feasible && l < L) ? span[Lmax + l] : -1;
+        if (tok_start) tok_start[(long)b * Lmax + l] = st;
+        if (tok_end) tok_end[(long)b * Lmax + l] = en;
+        if (tok_logp) {
+            float acc = 0.f;
+            if (st >= 0) for (int t = st; t <= en; ++t) acc += lp_rows[(long)t * Sp + 2 * l + 1];
+            tok_logp[(long)b * Lmax + l] = acc * CTC_LN2;
+        }
+    }
+}
+
+template <int NS, int CH, bool LDS_BP>
+__global__ __launch_bounds__(64) void ctc_align_kernel(int T, const int* __restrict__ hlens, const int* __restrict__ targets, int Lmax,
+                                                       const int* __restrict__ tlens, int Sp, const float* __restrict__ lp,
+                                                       void* __restrict__ bp_ws, int* __restrict__ frames, int* __restrict__ tok_start,
+                                                       int* __restrict__ tok_end, float* __restrict__ tok_logp, float* __restrict__ score) {
+    typedef typename std::conditional<(NS <= 4), unsigned char, unsigned short>::type BPT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char align_sh[];      // back-pointer words (LDS route)
+    __shared__ int span[64 * CTC_MAXQ];                                            // 2 * Lmax = Sp - 1 entries
+    const int b = blockIdx.x;
+    const int Tb = min(hlens[b], T);
+    const int L = max(min(tlens[b], Lmax), 0);
+    const int* tg = targets + (long)b * Lmax;
+    const float* lp_rows = lp + (long)b * T * Sp;
+    if (LDS_BP) {
+        BPT* bpl = reinterpret_cast<BPT*>(align_sh) + threadIdx.x;
+        ctc_align_wave<NS, CH>(bpl, span, b, T, Tb, L, Lmax, Sp, tg, lp_rows, frames, tok_start, tok_end, tok_logp, score);
+    } else {
+        BPT* bpl = reinterpret_cast<BPT*>(bp_ws) + (size_t)b * T * 64 + threadIdx.x;
+        ctc_align_wave<NS, CH>(bpl, span, b, T, Tb, L, Lmax, Sp, tg, lp_rows, frames, tok_start, tok_end, tok_logp, score);
+    }
+}
+
+// bytes of a back-pointer word (see ctc_align_kernel) and whether T frames of 64 of them go to LDS
+static inline size_t ctc_align_word(int Sp) { return Sp <= 256 ? 1 : 2; }
+static inline bool ctc_align_in_lds(int T, int Sp) { return (size_t)T * 64 * ctc_align_word(Sp) <= CTC_ALIGN_LDS; }
+
+extern "C" size_t oe_ctc_align_workspace_bytes(int B, int T, int Lmax) {
+    if (B <= 0 || T <= 0 || Lmax < 0) return 0;
+    const int Sp = 2 * Lmax + 1;
+    const size_t lp = ((size_t)B * T * Sp * sizeof(float) + 15) & ~(size_t)15;
+    return lp + (ctc_align_in_lds(T, Sp) ? 0 : (size_t)B * T * 64 * ctc_align_word(Sp));
+}
+
+extern "C" int oe_ctc_align(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets, int Lmax,
+                            const int* tlens, int* frames, int* tok_start, int* tok_end, float* tok_logp, float* score,
+                            void* workspace, void* stream) {
+    OE_REQUIRE(logits && hlens && tlens && frames && score && workspace, "oe_ctc_align: null pointer");
+    OE_REQUIRE(targets || Lmax == 0, "oe_ctc_align: null targets");
+    OE_REQUIRE(B > 0 && T > 0 && V > 1 && Lmax >= 0 && ldv >= V, "oe_ctc_align: bad shape B=%d T=%d V=%d Lmax=%d ldv=%ld", B, T, V, Lmax, ldv);
+    const int Sp = 2 * Lmax + 1;
+    OE_REQUIRE(Sp <= 64 * CTC_MAXQ, "oe_ctc_align: target length %d exceeds the 255-label limit of the wave recursion", Lmax);
+    hipStream_t st = (hipStream_t)stream;
+    float* lp = reinterpret_cast<float*>(workspace);
+    void* bp = reinterpret_cast<char*>(workspace) + (((size_t)B * T * Sp * sizeof(float) + 15) & ~(size_t)15);
+    const long rows = (long)B * T;
+    const bool vec = (((uintptr_t)logits & 15) == 0) && (ldv % 4 == 0) && (ldv >= (((long)V + 3) & ~3L)) && V <= 256 * 32;
+    const int nv4 = !vec ? 0 : V <= 256 * 4 ? 4 : V <= 256 * 8 ? 8 : V <= 256 * 16 ? 16 : 32;
+#define ROWS(NV4) hipLaunchKernelGGL((ctc_rows_kernel<NV4, false>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, hlens, targets, \
+                                     Lmax, tlens, Sp, 0.f, nullptr, lp, nullptr, 0, T, nullptr)
+    switch (nv4) {
+        case 4: ROWS(4); break;
+        case 8: ROWS(8); break;
+        case 16: ROWS(16); break;
+        case 32: ROWS(32); break;
+        default: ROWS(0); break;
+    }
+#undef ROWS
+    OE_LAUNCH_CHECK("ctc_align_rows");
+    const bool in_lds = ctc_align_in_lds(T, Sp);
+    const size_t shm = in_lds ? (size_t)T * 64 * ctc_align_word(Sp) : 0;
+#define AL(NS, CH, LDS) hipLaunchKernelGGL((ctc_align_kernel<NS, CH, LDS>), dim3(B), dim3(64), shm, st, T, hlens, targets, Lmax, tlens, Sp, lp, bp, \
+                                           frames, tok_start, tok_end, tok_logp, score)
+#define ALS(NS, CH) do { if (in_lds) AL(NS, CH, true); else AL(NS, CH, false); } while (0)
+    if (Sp <= 64) ALS(1, 32); else if (Sp <= 128) ALS(2, 16); else if (Sp <= 256) ALS(4, 8); else ALS(8, 4);
+#undef ALS
+#undef AL
+    OE_LAUNCH_CHECK("ctc_align");
     return 0;
 }

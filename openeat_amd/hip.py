@@ -218,6 +218,8 @@ _SIGNATURES = {
     "oe_ctc_loss_fused": (I, [P, L, I, I, I, P, P, I, P, F, P, P, P, P, P, P]),
     "oe_ctc_loss_fused_stats": (I, [P, L, I, I, I, P, P, I, P, F, P, P, P, P, P, P, I, P]),
     "oe_ctc_greedy": (I, [P, L, I, I, I, P, I, P, P, P, P]),
+    "oe_ctc_align_workspace_bytes": (SZ, [I, I, I]),
+    "oe_ctc_align": (I, [P, L, I, I, I, P, P, I, P, P, P, P, P, P, P, P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),

@@ -4,6 +4,7 @@
 targets_length) -> (loss, acc)``, the four decoding entry points, and the same
 flat state-dict keys.  All tensor arithmetic runs in the gfx950 kernels."""
 from collections import defaultdict
+import math
 import os
 from typing import List, Optional, Tuple
 
@@ -16,6 +17,7 @@ from openeat_amd.modules.ctc import CTC
 from openeat_amd.modules.decoder import BiTransformerDecoder
 from openeat_amd.modules.encoder import TransformerEncoder
 from openeat_amd.modules.label_smoothing_loss import LabelSmoothingLoss
+from openeat_amd.utils.align import frame_times
 from openeat_amd.utils.cmvn import load_cmvn
 from openeat_amd.utils.common import (IGNORE_ID, add_sos_eos, log_add, remove_duplicates_and_blank, reverse_pad_list)
 from openeat_amd.utils.mask import make_pad_mask, mask_finished_preds, mask_finished_scores, subsequent_mask
@@ -239,6 +241,42 @@ class ASRModel(torch.nn.Module):
         toks, n = ops.ctc_greedy(logits, V, B, T, V, lens, self.eos)
         toks, n = toks.cpu(), n.cpu()
         return [toks[b, : int(n[b])].tolist() for b in range(B)]
+
+    @torch.no_grad()
+    def ctc_align(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
+                  targets_length: torch.Tensor, with_times: bool = False, frame_shift_ms: float = 10):
+        """CTC forced alignment of each utterance to its own target (the reference has none; semantics in
+        include/openeat_hip.h): recursion and back-trace on the device, one D2H copy of the results.  Per utterance a dict
+        `frames` (token id of every valid encoder frame, 0 = blank), `tokens` (one dict per label: `token`, `start_frame`,
+        `end_frame` (inclusive), `confidence` = exp(mean log-prob over the span), and with_times `start_s` / `end_s`),
+        `score` (log-prob of the path); None for an utterance whose target does not fit its frames."""
+        assert features.shape[0] == features_length.shape[0] == targets.shape[0] == targets_length.shape[0]
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1)
+        frames, start, end, logp, score = self.ctc.forced_align(encoder_out, lens, targets, targets_length)
+        B, T = frames.shape
+        Lmax = start.shape[1]
+        cols = [frames, start, end, logp, targets[:, :Lmax], score.unsqueeze(1), lens.unsqueeze(1), targets_length.unsqueeze(1)]
+        packed = torch.cat([c.double() for c in cols], dim=1).cpu()          # (int32 and float32 are exact in float64)
+        frames, start, end, logp, targets = (packed[:, :T].long(), packed[:, T:T + Lmax].long(), packed[:, T + Lmax:T + 2 * Lmax].long(),
+                                             packed[:, T + 2 * Lmax:T + 3 * Lmax], packed[:, T + 3 * Lmax:T + 4 * Lmax].long())
+        score, lens, targets_length = packed[:, -3], packed[:, -2].long(), packed[:, -1].long()
+        rate = self.encoder.embed.subsampling_rate
+        out = []
+        for b in range(B):
+            if score[b] == float("-inf"):
+                out.append(None)
+                continue
+            toks = []
+            for l in range(int(targets_length[b])):
+                s, e = int(start[b, l]), int(end[b, l])
+                tok = {"token": int(targets[b, l]), "start_frame": s, "end_frame": e,
+                       "confidence": math.exp(float(logp[b, l]) / (e - s + 1))}
+                if with_times:
+                    tok["start_s"], tok["end_s"] = frame_times(s, e, rate, frame_shift_ms)
+                toks.append(tok)
+            out.append({"frames": frames[b, : int(lens[b])].tolist(), "tokens": toks, "score": float(score[b])})
+        return out
 
     def _ctc_prefix_beam_search(self, features, features_length, beam_size: int):
         """asr_model.py:328-396 (batch of one): log-probs and per-frame top-k on the device, the prefix

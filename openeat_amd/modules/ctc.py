@@ -36,3 +36,11 @@ class CTC(torch.nn.Module):
         from openeat_amd import hip
         hip.call("oe_ctc_greedy", lg, V, B, T, V, full, V - 1, fb, ot, ol)
         return fb.long()
+
+    def forced_align(self, hs_pad: torch.Tensor, hlens: torch.Tensor, ys_pad: torch.Tensor, ys_lens: torch.Tensor):
+        """Best CTC path of each utterance through its own target (the trellis of ctc.py:27-45 with max for the sum; the
+        reference has no aligner).  ys_pad (B, Lmax): padding beyond ys_lens is never read.  Returns device tensors
+        (frames, start, end, tok_logp, score), see ops.ctc_align."""
+        lg = self.logits(hs_pad)
+        B, T, V = lg.shape
+        return ops.ctc_align(lg, V, B, T, V, hlens, ys_pad, ys_lens)

@@ -2342,6 +2342,28 @@ def ctc_greedy(logits, ldv, B, T, V, hlens, eos):
     return ot, ol
 
 
+def ctc_align(logits, ldv, B, T, V, hlens, ys, ylens):
+    """CTC forced alignment (oe_ctc_align; semantics in include/openeat_hip.h): logits (B, T, ldv) float32, ys (B, Lmax)
+    labels of which ylens[b] count -> device tensors (frames (B, T) int32, start (B, Lmax) int32, end (B, Lmax) int32,
+    tok_logp (B, Lmax) float32, score (B) float32)."""
+    logits = _chk(logits, "ctc_align")
+    dev = logits.device
+    Lmax = int(ys.shape[1])
+    ys32 = ys.to(torch.int32).contiguous()
+    if Lmax == 0:                               # the C ABI wants a row per utterance; nothing of it is read
+        ys32 = torch.zeros(B, 1, dtype=torch.int32, device=dev)
+    Lk = max(Lmax, 1)
+    hl32, yl32 = hlens.to(torch.int32).contiguous(), ylens.to(torch.int32).contiguous()
+    frames = torch.empty(B, T, dtype=torch.int32, device=dev)
+    start = torch.empty(B, Lk, dtype=torch.int32, device=dev)
+    end = torch.empty(B, Lk, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(B, Lk, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(hip.lib().oe_ctc_align_workspace_bytes(B, T, Lk), dtype=torch.uint8, device=dev)
+    hip.call("oe_ctc_align", logits, ldv, B, T, V, hl32, ys32, Lk, yl32, frames, start, end, tok_logp, score, ws)
+    return frames, start[:, :Lmax], end[:, :Lmax], tok_logp[:, :Lmax], score
+
+
 def topk_rows(x, k: int, log_softmax: bool = False):
     """`x.topk(k)` over the last dim - of log_softmax(x) when asked - in one kernel (asr_model.py:251, 258, 358).
     Returns (values float32, indices int64), sorted descending; ties go to the lowest index."""
