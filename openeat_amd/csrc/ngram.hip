@@ -1,0 +1,190 @@
+// Back-off n-gram (ARPA) language-model scores of all B x beam hypotheses on the device, one wavefront per hypothesis
+// (the reference's openeat/models/asr_model.py:515-516: `lm.score(' '.join(content), bos=True, eos=True)` per hypothesis on
+// the host, with kenlm).  Semantics in include/openeat_hip.h; the host twin is openeat_amd/models/ngram_lm.py.
+//
+// Lookup structure: chained exact keys in one open-addressing table (linear probing, power-of-two capacity >= 2 x the
+// number of n-grams of order >= 2, i.e. load factor <= 0.5).  Every listed n-gram has an entry number: a unigram's is its
+// word id, an n-gram of order >= 2 has n_words + the slot it sits in.  Its key is (entry of its first k-1 words) << 32 |
+// (id of its k-th word): the key IS the n-gram, no hash is ever compared, so a listed n-gram is found exactly and an
+// unlisted one is never mistaken for a listed one.  A slot is 16 bytes {key, log10 p, back-off}: one load answers a
+// probe.  The builder records the longest displacement any key has (max_probe); a lookup ends at the key, at an empty
+// slot, or after max_probe + 1 slots, whichever comes first, and every slot index is masked by capacity - 1.
+//
+// What is parallel.  The term of position i is  logp(w[i-k+1..i])  for the longest listed k  plus the back-offs of the
+// contexts w[i-j+1..i-1], j > k, that are listed.  All of these are properties of the n-grams that START at some
+// position s: the chain  w[s], w[s..s+1], .. w[s..s+order-1]  (each found from the one before, so order-1 dependent
+// probes, stopping at the first that is not listed - the reader guarantees that a listed n-gram's prefix is listed).  So
+// a lane walks the chain of ONE start position and leaves (how many were found, their log10 p, their back-offs) in LDS;
+// then a lane collects the term of ONE scored position from the order chains that cover it.  That is order-1 probes per
+// position instead of the order (order+1) / 2 - 1 a per-position search makes, and the 64 chains of a tile are
+// independent loads in flight together.  Tiles of 64 positions; the last order-1 chains of a tile stay in LDS for the next.
+// Sums are float64: a lane adds its positions' terms in tile order, then a xor-butterfly over the wave - a fixed order,
+// so a score is the same bits on every run.  No atomics.
+//
+// Bound: latency.  A hypothesis of L tokens is ceil((L + 2) / 64) tiles of order-1 dependent 16-byte gathers into a table
+// that does not fit LDS (32 MiB for a million n-grams); the bytes moved are a few MB per call.
+#include <math.h>
+#include "oe_common.h"
+#include "../../include/openeat_hip.h"
+
+#define NG_MAXORDER 5
+#define NG_TILE 64
+#define NG_COLS (NG_TILE + NG_MAXORDER - 1)
+#define NG_EMPTY 0xFFFFFFFFFFFFFFFFull
+
+struct NgSlot {            // one 16-byte slot of the table
+    unsigned long long key;
+    float logp, backoff;
+};
+
+__device__ __forceinline__ unsigned long long ng_mix(unsigned long long x) {      // murmur3's 64-bit finaliser
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// slot of `key`, or -1; at most max_probe + 1 slots are read, every index is < cap
+__device__ __forceinline__ long ng_find(const uint4* __restrict__ table, unsigned long long mask, int max_probe,
+                                        unsigned long long key, float& logp, float& backoff) {
+    unsigned long long slot = ng_mix(key) & mask;
+    for (int d = 0; d <= max_probe; ++d) {
+        const uint4 v = table[slot];
+        const unsigned long long k = ((unsigned long long)v.y << 32) | v.x;
+        if (k == key) { logp = __uint_as_float(v.z); backoff = __uint_as_float(v.w); return (long)slot; }
+        if (k == NG_EMPTY) return -1;
+        slot = (slot + 1) & mask;
+    }
+    return -1;
+}
+
+__device__ __forceinline__ double ng_shfl_xor(double v, int o) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_xor(lo, o, 64);
+    hi = __shfl_xor(hi, o, 64);
+    return __hiloint2double(hi, lo);
+}
+
+__global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restrict__ unigrams, int n_words,
+                                                         const uint4* __restrict__ table, unsigned long long mask, int max_probe,
+                                                         int order, int bos_word, int eos_word, int unk_word,
+                                                         const int* __restrict__ tok2word, int V, const int* __restrict__ tokens,
+                                                         long ld, const int* __restrict__ lens, int bos, int eos,
+                                                         double* __restrict__ score, double* __restrict__ tok_logp,
+                                                         int* __restrict__ tok_order) {
+    __shared__ int wd[NG_COLS];                                  // word ids of positions base .. base + 63 + (order-1)
+    __shared__ int found[NG_COLS];                               // column c = start position base - (NG_MAXORDER-1) + c
+    __shared__ float lp[NG_MAXORDER][NG_COLS], bo[NG_MAXORDER][NG_COLS];
+
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int len_raw = lens[r];
+    if (len_raw < 0) {                                           // the slot does not exist (wave-uniform)
+        if (lane == 0) score[r] = -__builtin_huge_val();
+        return;
+    }
+    const int len = (int)min((long)len_raw, ld);
+    const int off = bos ? 1 : 0;
+    const int P = off + len + (eos ? 1 : 0);                     // positions: [<s>] tokens [</s>]; scored: off .. P-1
+    const int* tk = tokens + (long)r * ld;
+    const int H = NG_MAXORDER - 1;
+
+    if (lane < H) found[lane] = 0;                               // no chain starts before position 0
+    double acc = 0.0;
+    for (int base = 0; base < P; base += NG_TILE) {
+        // ---- word ids of the tile and of the order-1 positions after it
+        for (int c = lane; c < NG_COLS; c += NG_TILE) {
+            const int q = base + c;
+            int w = -1;
+            if (q < P) {
+                if (q < off) w = bos_word;
+                else if (q - off < len) {
+                    const int t = tk[q - off];
+                    w = (t >= 0 && t < V) ? tok2word[t] : unk_word;
+                    if (w < 0 || w >= n_words) w = unk_word;
+                } else w = eos_word;
+            }
+            wd[c] = w;
+        }
+        __syncthreads();
+        // ---- the chain that starts at position s = base + lane
+        {
+            const int s = base + lane;
+            int nf = 0;
+            if (s < P) {
+                long e = wd[lane];
+                const float2 u = unigrams[e];
+                lp[0][H + lane] = u.x; bo[0][H + lane] = u.y;
+                nf = 1;
+                for (int k = 2; k <= order; ++k) {
+                    if (s + k - 1 >= P) break;
+                    const unsigned long long key = ((unsigned long long)e << 32) | (unsigned)wd[lane + k - 1];
+                    float a = 0.f, b = 0.f;
+                    const long slot = ng_find(table, mask, max_probe, key, a, b);
+                    if (slot < 0) break;
+                    lp[k - 1][H + lane] = a; bo[k - 1][H + lane] = b;
+                    e = (long)n_words + slot;
+                    nf = k;
+                }
+            }
+            found[H + lane] = nf;
+        }
+        __syncthreads();
+        // ---- the term of position i = base + lane: longest listed n-gram ending at i, back-offs of the longer contexts
+        {
+            const int i = base + lane;
+            if (i >= off && i < P) {
+                double term = 0.0;
+                int k = min(order, i + 1);
+                for (; k > 1; --k) {
+                    const int c = H + lane - (k - 1);            // chain that starts at i - k + 1
+                    const int nf = found[c];
+                    if (nf >= k) break;
+                    if (nf >= k - 1) term += (double)bo[k - 2][c];        // its context w[i-k+1 .. i-1] is listed
+                }
+                term += (double)lp[k - 1][H + lane - (k - 1)];
+                acc += term;
+                const long o = (long)r * (ld + 1) + (i - off);
+                if (tok_logp) tok_logp[o] = term;
+                if (tok_order) tok_order[o] = k;
+            }
+        }
+        __syncthreads();
+        // ---- keep the last order-1 chains for the next tile
+        float keep_lp[NG_MAXORDER], keep_bo[NG_MAXORDER];
+        int keep_f = 0;
+        if (lane < H) {
+            keep_f = found[NG_TILE + lane];
+#pragma unroll
+            for (int k = 0; k < NG_MAXORDER; ++k) { keep_lp[k] = lp[k][NG_TILE + lane]; keep_bo[k] = bo[k][NG_TILE + lane]; }
+        }
+        __syncthreads();
+        if (lane < H) {
+            found[lane] = keep_f;
+#pragma unroll
+            for (int k = 0; k < NG_MAXORDER; ++k) { lp[k][lane] = keep_lp[k]; bo[k][lane] = keep_bo[k]; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += ng_shfl_xor(acc, o);
+    if (lane == 0) score[r] = acc;
+}
+
+extern "C" int oe_ngram_score(const float* unigrams, int n_words, const void* table, long capacity, int max_probe, int order,
+                              int bos_word, int eos_word, int unk_word, const int* tok2word, int V, const int* tokens, long ld,
+                              const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order,
+                              void* stream) {
+    OE_REQUIRE(unigrams && table && tok2word && tokens && lens && score, "oe_ngram_score: null pointer");
+    OE_REQUIRE(order >= 1 && order <= NG_MAXORDER, "oe_ngram_score: order must be 1..%d (got %d)", NG_MAXORDER, order);
+    OE_REQUIRE(capacity >= 2 && (capacity & (capacity - 1)) == 0, "oe_ngram_score: capacity must be a power of two >= 2 (got %ld)", capacity);
+    OE_REQUIRE(max_probe >= 0 && max_probe < capacity, "oe_ngram_score: bad max_probe %d", max_probe);
+    OE_REQUIRE(n_words > 0 && (long)n_words + capacity < 0x7fffffffL, "oe_ngram_score: n_words + capacity must stay below 2^31");
+    OE_REQUIRE(bos_word >= 0 && bos_word < n_words && eos_word >= 0 && eos_word < n_words && unk_word >= 0 && unk_word < n_words,
+               "oe_ngram_score: <s> / </s> / <unk> ids outside the vocabulary");
+    OE_REQUIRE(R >= 0 && V > 0 && ld >= 0, "oe_ngram_score: bad shape R=%d V=%d ld=%ld", R, V, ld);
+    if (R == 0) return 0;
+    hipLaunchKernelGGL(ngram_score_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, (const float2*)unigrams, n_words,
+                       (const uint4*)table, (unsigned long long)(capacity - 1), max_probe, order, bos_word, eos_word, unk_word,
+                       tok2word, V, tokens, ld, lens, bos, eos, score, tok_logp, tok_order);
+    OE_LAUNCH_CHECK("ngram_score");
+    return 0;
+}

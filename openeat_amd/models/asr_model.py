@@ -12,6 +12,7 @@ import torch
 
 from openeat_amd import ops
 from openeat_amd import planes as _planes
+from openeat_amd.models.ngram_lm import NgramLM
 from openeat_amd.modules.cmvn import GlobalCMVN
 from openeat_amd.modules.ctc import CTC
 from openeat_amd.modules.decoder import BiTransformerDecoder
@@ -454,7 +455,9 @@ class ASRModel(torch.nn.Module):
             r_tok = torch.cat([r_ori.long(), ori.new_full((R, L - Lm), self.ignore_id)], 1).clamp(min=0)
             score = score * (1 - reverse_weight) + seq_score(r_x, r_tok) * reverse_weight
         score = score + ctc_scores * ctc_weight
-        if lm is not None and lm_weight > 0:                                      # neural-LM shallow fusion (asr_model.py:490-527)
+        if isinstance(lm, NgramLM) and lm_weight > 0:                             # n-gram LM (asr_model.py:515-516, 528): log10, as kenlm's
+            score = score + ops.ngram_score(lm, ori, hl) * lm_weight
+        elif lm is not None and lm_weight > 0:                                    # neural-LM shallow fusion (asr_model.py:490-527)
             lm_tok = ops.logprob_gather(lm.logits(hyps_pad, hl + 1), tok) if hasattr(lm, "logits") else \
                 lm.log_probs(hyps_pad, hl + 1).gather(2, tok.unsqueeze(2)).squeeze(2)
             score = score + (lm_tok * valid).sum(1).double() * lm_weight

@@ -2364,6 +2364,29 @@ def ctc_align(logits, ldv, B, T, V, hlens, ys, ylens):
     return frames, start[:, :Lmax], end[:, :Lmax], tok_logp[:, :Lmax], score
 
 
+def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
+    """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
+    openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:
+    the slot does not exist, score -inf; what lies behind a length is not read) -> score (R) float64, total log10
+    probability.  per_token: also (tok_logp (R, ld+1) float64, tok_order (R, ld+1) int32), zero where nothing is written.
+    No host read, no allocation beyond the outputs: capturable."""
+    if not (isinstance(tokens, torch.Tensor) and isinstance(lens, torch.Tensor) and tokens.is_cuda and lens.is_cuda):
+        raise TypeError("ngram_score: openeat_amd ops need CUDA tensors; there is no CPU fallback (on the host: NgramLM.score)")
+    if tokens.dtype.is_floating_point or lens.dtype.is_floating_point or tokens.dim() != 2 or lens.shape != tokens.shape[:1]:
+        raise TypeError("ngram_score: tokens (R, ld) and lens (R) must be integer tensors")
+    dev = tokens.device
+    uni, table, tok2word = lm.device_tables(dev)
+    R, ld = int(tokens.shape[0]), int(tokens.shape[1])
+    tok32 = tokens.to(torch.int32).contiguous()
+    len32 = lens.to(torch.int32).contiguous()
+    score = torch.empty(R, dtype=torch.float64, device=dev)
+    tok_logp = torch.zeros(R, ld + 1, dtype=torch.float64, device=dev) if per_token else None
+    tok_order = torch.zeros(R, ld + 1, dtype=torch.int32, device=dev) if per_token else None
+    hip.call("oe_ngram_score", uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word,
+             tok2word, int(tok2word.shape[0]), tok32, ld, len32, R, int(bool(bos)), int(bool(eos)), score, tok_logp, tok_order)
+    return (score, tok_logp, tok_order) if per_token else score
+
+
 def topk_rows(x, k: int, log_softmax: bool = False):
     """`x.topk(k)` over the last dim - of log_softmax(x) when asked - in one kernel (asr_model.py:251, 258, 358).
     Returns (values float32, indices int64), sorted descending; ties go to the lowest index."""
