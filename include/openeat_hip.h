@@ -711,6 +711,32 @@ int oe_ngram_score(const float* unigrams, int n_words, const void* table, long c
                    int bos_word, int eos_word, int unk_word, const int* tok2word, int V, const int* tokens, long ld,
                    const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order, void* stream);
 
+/* Batched edit distance on the device, one wavefront per pair: the counts behind the reference's error-rate table
+ * (tools/compute-wer.py, Calculator.calculate) and optionally the alignment.  These are the semantics every layer refers to.
+ * For a reference r[0..n) and a hypothesis h[0..m) of token ids, costs cor 0, sub 1, del 1, ins 1:
+ *   D[i][0] = i (all deletions), D[0][j] = j (all insertions);
+ *   for i, j >= 1 the predecessor is chosen in the order deletion (i-1, j), insertion (i, j-1), diagonal (i-1, j-1)
+ *   (cor if r[i-1] == h[j-1], else sub); a later candidate replaces the best only if it is strictly smaller;
+ *   the alignment is the chain of chosen predecessors from (n, m) back to (0, 0); cor, sub, del, ins count its moves, so
+ *   cor + sub + del = n and the error rate is (sub + del + ins) / n.
+ * Pair p compares hyp row p (hyp_lens[p] tokens) with ref row p / group (ref_lens[p / group] tokens): group = 1 is
+ * one-to-one, group = beam an n-best list against its utterance.  ref (P / group, ref_ld), hyp (P, hyp_ld) i32; what lies at
+ * or behind a row's length never reaches a result.  hyp_lens[p] < 0 = the slot does not exist (as out_len of
+ * oe_ctc_prefix_beam): counts (-1, -1, -1, -1), every ref_to_hyp entry -1.
+ *   out: counts (P, 4) i32 = cor, sub, del, ins;  ref_to_hyp (P, Nmax) i32 or NULL: the hypothesis position aligned with
+ *        reference token i (cor or sub), -1 if it is deleted, -1 for i >= n; inserted hypothesis tokens are those no entry names.
+ *   0 <= Nmax, Mmax <= 1023; group >= 1, P % group == 0, ref_ld >= Nmax, hyp_ld >= Mmax - anything else, and a null required
+ *   pointer, is reported through oe_last_error before any launch.  The lengths live on the device: one above its maximum is
+ *   clamped to it by the kernel (a negative ref length counts as 0).
+ *   workspace: oe_edit_distance_workspace_bytes(P, Nmax, Mmax) bytes, 4-byte aligned; 0 (NULL allowed) when ref_to_hyp is NULL
+ *   or the 2-bit back-pointers fit LDS (Nmax * ceil(Mmax / 16) * 4 <= 48 KiB).
+ * With ref_to_hyp == NULL the counts are carried forward along the chosen predecessors and no workspace is touched.
+ * One launch; no atomics, no allocation, no synchronisation, no host-side state: capturable. */
+size_t oe_edit_distance_workspace_bytes(int P, int Nmax, int Mmax);
+int oe_edit_distance(const int* ref, long ref_ld, const int* ref_lens, int group, const int* hyp, long hyp_ld,
+                     const int* hyp_lens, int P, int Nmax, int Mmax, int* counts, int* ref_to_hyp, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,6 +268,8 @@ _SIGNATURES = {
     "oe_ctc_prefix_beam_host": (I, [P, P, I, I, I, P, P, P]),
     "oe_ctc_prefix_beam_host_batch": (I, [P, P, I, I, P, I, I, P, P, P, I]),
     "oe_ngram_score": (I, [P, I, P, L, I, I, I, I, I, P, I, P, L, P, I, I, I, P, P, P, P]),
+    "oe_edit_distance_workspace_bytes": (SZ, [I, I, I]),
+    "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_grad_norm_workspace_floats": (SZ, []),
     "oe_grad_norm": (I, [P, L, P, P, P]),
     "oe_adam_step": (I, [P, P, P, P, L, P, F, F, F, F, F, P, P, P]),

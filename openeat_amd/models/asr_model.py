@@ -29,6 +29,7 @@ from openeat_amd.utils.mask import make_pad_mask, mask_finished_preds, mask_fini
 DEVICE_BEAM = os.environ.get("OE_DEVICE_BEAM", "1") != "0"
 DECODE_GRAPHS = os.environ.get("OE_DECODE_GRAPHS", "0") == "1"
 DECODE_GRAPH_SLOTS = 8
+EDIT_DISTANCE_MAX = 1023                                                     # oe_edit_distance: columns per sequence
 ATT_INPUTS_KERNEL = os.environ.get("OE_ATT_INPUTS_KERNEL", "1") != "0"      # decoder token bookkeeping as one launch (fixed widths)
 
 
@@ -277,6 +278,46 @@ class ASRModel(torch.nn.Module):
                     tok["start_s"], tok["end_s"] = frame_times(s, e, rate, frame_shift_ms)
                 toks.append(tok)
             out.append({"frames": frames[b, : int(lens[b])].tolist(), "tokens": toks, "score": float(score[b])})
+        return out
+
+    @torch.no_grad()
+    def error_counts(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
+                     targets_length: torch.Tensor, mode: str = "ctc_greedy_search", beam_size: int = 10,
+                     nbest_oracle: bool = False, **decode_kwargs) -> dict:
+        """Decode and score against the targets on the device (ops.edit_distance; the counts of the reference's
+        tools/compute-wer.py, semantics in include/openeat_hip.h).  Returns device tensors: `counts` (B, 4) int32 = cor, sub,
+        del, ins per utterance, and with nbest_oracle (attention_rescoring on the device beam) `oracle_counts` (B, 4) /
+        `oracle_index` (B): the n-best slot with the fewest errors.  Only targets_length is trusted, not the padding.
+        ctc_greedy_search reads nothing back; attention_rescoring scores the lists attention_rescoring_batch(**decode_kwargs)
+        returns, and nbest_oracle runs the encoder and the prefix beam a second time for the n-best lists (the batched call
+        does not hand them out).  The token matrices are as wide as the encoder output; oe_edit_distance takes 1023 columns, so
+        of a hypothesis longer than that (more than 41 s of audio decoded to a token per frame) the first 1023 tokens count."""
+        from openeat_amd.utils.error_rate import nbest_oracle as oracle_of
+        assert features.shape[0] == features_length.shape[0] == targets.shape[0] == targets_length.shape[0]
+        device = features.device
+        if mode == "ctc_greedy_search":
+            if nbest_oracle:
+                raise ValueError("error_counts: ctc_greedy_search has no n-best list")
+            encoder_out, encoder_mask, _ = self._encode(features, features_length)
+            lens = encoder_mask.squeeze(1).sum(1)
+            logits = self.ctc.logits(encoder_out)
+            B, T, V = logits.shape
+            toks, n = ops.ctc_greedy(logits, V, B, T, V, lens, self.eos)
+            return {"counts": ops.edit_distance(targets, targets_length, toks[:, :EDIT_DISTANCE_MAX], n)}
+        if mode != "attention_rescoring":
+            raise ValueError(f"error_counts: unknown mode {mode!r}")
+        if nbest_oracle and not (DEVICE_BEAM and beam_size <= 16):
+            raise NotImplementedError("error_counts: nbest_oracle needs the device beam (OE_DEVICE_BEAM=1, beam_size <= 16)")
+        hyps = self.attention_rescoring_batch(features, features_length, beam_size, **decode_kwargs)
+        hl = [len(h) for h in hyps]
+        pad = torch.full((len(hyps), max(hl + [0])), self.ignore_id, dtype=torch.int32)
+        for b, h in enumerate(hyps):
+            pad[b, : hl[b]] = torch.tensor(h, dtype=torch.int32)
+        out = {"counts": ops.edit_distance(targets, targets_length, pad.to(device), torch.tensor(hl, dtype=torch.int32).to(device))}
+        if nbest_oracle:
+            _, _, pre, plen, _, _ = self._rescore_stage1(features, features_length, beam_size)
+            out["oracle_counts"], out["oracle_index"] = oracle_of(
+                ops.edit_distance(targets, targets_length, pre[:, :EDIT_DISTANCE_MAX], plen, group=beam_size), beam_size)
         return out
 
     def _ctc_prefix_beam_search(self, features, features_length, beam_size: int):

@@ -2387,6 +2387,40 @@ def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token:
     return (score, tok_logp, tok_order) if per_token else score
 
 
+def edit_distance(ref, ref_lens, hyp, hyp_lens, group: int = 1, align: bool = False):
+    """Edit distance of P (reference, hypothesis) pairs on the device (oe_edit_distance; semantics and tie order in
+    include/openeat_hip.h): ref (P / group, Nmax) and hyp (P, Mmax) integer token ids, ref_lens (P / group) and hyp_lens (P)
+    their lengths, all on the device; pair p compares hyp row p with ref row p // group.  What lies behind a length is not
+    read into the result; hyp_lens[p] < 0: the slot does not exist, its row is all -1.  -> counts (P, 4) int32 = cor, sub,
+    del, ins; align: also ref_to_hyp (P, Nmax) int32, the hypothesis position of each reference token (-1: deleted or
+    beyond the length).  No host read: capturable."""
+    ts = (ref, ref_lens, hyp, hyp_lens)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError("edit_distance: openeat_amd ops need CUDA tensors; there is no CPU fallback")
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ts) or ref.dim() != 2 or hyp.dim() != 2 \
+            or ref_lens.shape != ref.shape[:1] or hyp_lens.shape != hyp.shape[:1]:
+        raise TypeError("edit_distance: ref (P / group, Nmax), hyp (P, Mmax) and their lengths must be integer tensors")
+    dev = hyp.device
+    P, Mmax, Nmax = int(hyp.shape[0]), int(hyp.shape[1]), int(ref.shape[1])
+    group = int(group)
+    if group < 1 or ref.shape[0] * group != P:
+        raise ValueError(f"edit_distance: {ref.shape[0]} references x group {group} != {P} hypotheses")
+    counts = torch.empty(P, 4, dtype=torch.int32, device=dev)
+    r2h = torch.empty(P, Nmax, dtype=torch.int32, device=dev) if align else None
+    if P == 0:
+        return (counts, r2h) if align else counts
+    ref32, hyp32 = ref.to(torch.int32).contiguous(), hyp.to(torch.int32).contiguous()
+    ws = None
+    if align:
+        nbytes = hip.lib().oe_edit_distance_workspace_bytes(P, Nmax, Mmax)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    # a zero-width matrix has no storage to point at: the C ABI takes NULL for it
+    hip.call("oe_edit_distance", ref32 if Nmax else None, Nmax, ref_lens.to(torch.int32).contiguous(), group,
+             hyp32 if Mmax else None, Mmax, hyp_lens.to(torch.int32).contiguous(), P, Nmax, Mmax, counts,
+             r2h if Nmax else None, ws)
+    return (counts, r2h) if align else counts
+
+
 def topk_rows(x, k: int, log_softmax: bool = False):
     """`x.topk(k)` over the last dim - of log_softmax(x) when asked - in one kernel (asr_model.py:251, 258, 358).
     Returns (values float32, indices int64), sorted descending; ties go to the lowest index."""

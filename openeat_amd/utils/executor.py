@@ -8,6 +8,7 @@ from torch.nn.utils import clip_grad_norm_
 
 from openeat_amd.optim import FusedAdam
 from openeat_amd.utils.common import map_to_device
+from openeat_amd.utils.error_rate import ErrorRate, overall_line
 
 
 class Executor:
@@ -87,6 +88,8 @@ class Executor:
         log_interval = args.get("log_interval", 10)
         num_seen_utts, total_loss, total_acc = 0, 0.0, 0.0
         n_batches = len(data_loader)
+        # cv_error_rate: also decode every batch greedily and score it on the device (a second encoder pass per batch)
+        error_rate = ErrorRate() if args.get("cv_error_rate") else None
         with torch.no_grad():
             for batch_idx, (keys, batch) in enumerate(data_loader):
                 batch = map_to_device(batch, device)
@@ -94,6 +97,8 @@ class Executor:
                 if num_utts == 0:
                     continue
                 loss, acc = model(**batch)
+                if error_rate is not None:
+                    error_rate.update(model.error_counts(**batch)["counts"])
                 loss = torch.mean(loss)
                 acc = None if acc is None else torch.mean(acc)
                 if torch.isfinite(loss):
@@ -107,4 +112,7 @@ class Executor:
                     if acc is not None:
                         msg += "Acc:{:.4f} AAcc:{:.4f} rank:{}".format(acc.item(), total_acc / max(num_seen_utts, 1), local_rank)
                     logger.info(msg)
+        if error_rate is not None:
+            self.last_cv_error_rate = error_rate.result()
+            logger.info("CV TER " + overall_line(self.last_cv_error_rate))
         return total_loss / max(num_seen_utts, 1), total_acc / max(num_seen_utts, 1)
