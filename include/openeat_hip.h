@@ -711,6 +711,37 @@ int oe_ngram_score(const float* unigrams, int n_words, const void* table, long c
                    int bos_word, int eos_word, int unk_word, const int* tok2word, int V, const int* tokens, long ld,
                    const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order, void* stream);
 
+/* CTC prefix beam search with n-gram LM shallow fusion on the device, one wavefront per utterance.  These are the semantics
+ * every layer refers to.  It is the algorithm of oe_ctc_prefix_beam (asr_model.py:359-396) with one change, the key that
+ * orders next_hyps before the cut to `beam`:
+ *   total(p) = log_add(pb, pnb) + lm_weight * LM(p) + length_bonus * len(p)
+ *   LM(p)    = sum over i < len(p), left to right in float64, of log10 p(word(p_i) | h_i)
+ * LM terms: p(w | h) is the ARPA back-off definition exactly as oe_ngram_score states it - h the up to order-1 previous
+ *   words, starting from <s>, which is context only and never scored; token -> word through tok2word; out-of-range ids count
+ *   as <unk>.  So LM(p) is oe_ngram_score(p, bos=1, eos=0) up to summation order.
+ * Units: log10, mixed in unconverted, as the reference and the rescoring do with kenlm's numbers.
+ * Per-frame updates: the pb / pnb updates are unchanged, the same arithmetic in the same visiting order; the CTC numbers
+ *   are the same bits as oe_ctc_prefix_beam's.
+ * Sort order: stable and descending by total, so ties keep insertion order (the first-touch stamp).
+ * LM(p) depends on the prefix only: the two routes that merge into one prefix carry the same value and the same LM state.
+ * End of the utterance: if eos, every surviving prefix gets LM += log10 p(</s> | its context); the <= beam survivors are
+ *   stably re-sorted by total.  An utterance of zero frames yields the one empty prefix, with LM = p(</s> | <s>) when eos.
+ * Outputs per (b, slot), device memory: out_prefix (B, beam, max_len) i32 and out_len (B, beam) i32 with -1 for a missing
+ *   slot; out_score = total, out_ctc = log_add(pb, pnb), out_lm = LM including the </s> term, each (B, beam) f64 and -inf
+ *   for a missing slot; the status word of the workspace as for oe_ctc_prefix_beam.
+ * Identity with zero weights: with lm_weight == 0 and length_bonus == 0 the n-best lists and their order are those of
+ *   oe_ctc_prefix_beam, and out_ctc equals its out_score bit for bit.
+ * topk_logp / topk_idx / lens / beam (<= 16) / max_len / workspace (oe_ctc_prefix_beam_lm_workspace_bytes bytes, last word
+ * zeroed by the caller) as for oe_ctc_prefix_beam; unigrams .. V the model arguments of oe_ngram_score (order <= 5);
+ * lm_weight and length_bonus finite.  Anything else, and a null pointer other than lens, is reported through oe_last_error
+ * before any launch.  One launch, no atomics other than the status word, no allocation, no host read: capturable. */
+size_t oe_ctc_prefix_beam_lm_workspace_bytes(int B, int Tmax, int beam);
+int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
+                          int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
+                          int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, double lm_weight,
+                          double length_bonus, int eos, void* workspace, int* out_prefix, int* out_len, double* out_score,
+                          double* out_ctc, double* out_lm, void* stream);
+
 /* Batched edit distance on the device, one wavefront per pair: the counts behind the reference's error-rate table
  * (tools/compute-wer.py, Calculator.calculate) and optionally the alignment.  These are the semantics every layer refers to.
  * For a reference r[0..n) and a hypothesis h[0..m) of token ids, costs cor 0, sub 1, del 1, ins 1:

@@ -175,7 +175,7 @@ class TnProblem(C.Structure):
                 ("block_start", C.c_int), ("reserved", C.c_int)]
 
 
-I, L, F, P, U64, SZ = C.c_int, C.c_long, C.c_float, c_fp, C.c_ulonglong, C.c_size_t
+I, L, F, D, P, U64, SZ = C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
     "oe_abi_version": (I, []),
@@ -268,6 +268,8 @@ _SIGNATURES = {
     "oe_ctc_prefix_beam_host": (I, [P, P, I, I, I, P, P, P]),
     "oe_ctc_prefix_beam_host_batch": (I, [P, P, I, I, P, I, I, P, P, P, I]),
     "oe_ngram_score": (I, [P, I, P, L, I, I, I, I, I, P, I, P, L, P, I, I, I, P, P, P, P]),
+    "oe_ctc_prefix_beam_lm_workspace_bytes": (SZ, [I, I, I]),
+    "oe_ctc_prefix_beam_lm": (I, [P, P, I, I, P, I, I, P, I, P, L, I, I, I, I, I, P, I, D, D, I, P, P, P, P, P, P, P]),
     "oe_edit_distance_workspace_bytes": (SZ, [I, I, I]),
     "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_grad_norm_workspace_floats": (SZ, []),
@@ -544,6 +546,38 @@ def ctc_prefix_beam_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: 
         raise RuntimeError("oe_ctc_prefix_beam: a prefix exceeded max_len")
     return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), float(scores[b, i])) for i in range(beam) if plen[b, i] >= 0]
             for b in range(B)]
+
+
+def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, lm,
+                              lm_weight: float, length_bonus: float = 0.0, eos: bool = True, raw: bool = False):
+    """CTC prefix beam search with n-gram LM shallow fusion (oe_ctc_prefix_beam_lm; semantics in include/openeat_hip.h): the
+    inputs of ctc_prefix_beam_device plus `lm`, an openeat_amd.models.ngram_lm.NgramLM -> per utterance
+    [(prefix tuple, total, ctc, lm)] sorted by total.  raw=True: no copy at all - the device tensors (prefixes (B, beam, T)
+    int32, lengths (B, beam) int32 with -1 for missing entries, total / ctc / lm (B, beam) float64, -inf where missing) and
+    the status word tensor the caller checks after its own synchronisation."""
+    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
+        raise TypeError("ctc_prefix_beam_lm_device: float32 / int64 CUDA tensors required")
+    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
+    B, T = top_logp.shape[0], top_logp.shape[1]
+    ml = max(T, 1)
+    dev = top_logp.device
+    uni, table, tok2word = lm.device_tables(dev)
+    ws = torch.empty(lib().oe_ctc_prefix_beam_lm_workspace_bytes(B, T, beam) // 4, dtype=torch.int32, device=dev)
+    ws[-1:].zero_()
+    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
+    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    total, ctc, lms = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(3))
+    call("oe_ctc_prefix_beam_lm", top_logp, top_idx, B, T, lens, beam, ml, uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order,
+         lm.bos_word, lm.eos_word, lm.unk_word, tok2word, int(tok2word.shape[0]), float(lm_weight), float(length_bonus),
+         int(bool(eos)), ws, prefixes, plen, total, ctc, lms)
+    if raw:
+        return prefixes, plen, total, ctc, lms, ws[-1:]
+    prefixes, plen, bad = prefixes.cpu().numpy(), plen.cpu().numpy(), int(ws[-1])
+    total, ctc, lms = total.cpu().numpy(), ctc.cpu().numpy(), lms.cpu().numpy()
+    if bad:
+        raise RuntimeError("oe_ctc_prefix_beam_lm: a prefix exceeded max_len")
+    return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), float(total[b, i]), float(ctc[b, i]), float(lms[b, i]))
+             for i in range(beam) if plen[b, i] >= 0] for b in range(B)]
 
 
 def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, lens, beam: int, n_threads: int = 0):

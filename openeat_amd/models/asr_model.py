@@ -33,6 +33,16 @@ EDIT_DISTANCE_MAX = 1023                                                     # o
 ATT_INPUTS_KERNEL = os.environ.get("OE_ATT_INPUTS_KERNEL", "1") != "0"      # decoder token bookkeeping as one launch (fixed widths)
 
 
+def _require_fused_beam(lm, beam_size):
+    """The LM-fused prefix search exists on the device only (beam_lm.hip): an NgramLM, the device beam, beam <= 16."""
+    if not isinstance(lm, NgramLM):
+        raise ValueError(f"the LM-fused CTC beam search needs an NgramLM (got {type(lm).__name__})")
+    if not DEVICE_BEAM:
+        raise ValueError("the LM-fused CTC beam search runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
+    if not 1 <= beam_size <= 16:
+        raise ValueError(f"the LM-fused CTC beam search supports beam sizes 1..16 (got {beam_size})")
+
+
 def _graph_call(cache, key, fn, args):
     """fn(*args) through a per-key HIP graph: first call eager (lazy state must exist before a capture) and captured for
     the next time, later calls copy the arguments into the capture's static inputs and replay.  Outputs are the capture's
@@ -336,6 +346,21 @@ class ASRModel(torch.nn.Module):
         hyps, _ = self._ctc_prefix_beam_search(features, features_length, beam_size)
         return hyps[0][0]
 
+    @torch.no_grad()
+    def ctc_lm_beam_search(self, features, features_length, beam_size: int, lm, lm_weight: float, length_bonus: float = 0.0,
+                           eos: bool = True):
+        """CTC prefix beam search with n-gram LM shallow fusion, batched (oe_ctc_prefix_beam_lm; semantics in
+        include/openeat_hip.h): prefixes are pruned every frame by log_add(pb, pnb) + lm_weight * LM + length_bonus * len.
+        -> per utterance [(prefix tuple, total, ctc, lm)] sorted by total.  Needs an NgramLM, the device beam and
+        beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
+        from openeat_amd import hip
+        _require_fused_beam(lm, beam_size)
+        assert features.shape[0] == features_length.shape[0]
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1)
+        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
+        return hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, lm, lm_weight, length_bonus, eos)
+
     def attention_rescoring(self, features, features_length, beam_size: int, ctc_weight: float = 0.0,
                             reverse_weight: float = 0.0, lm: Optional[torch.nn.Module] = None, lm_weight: float = 0,
                             autoregressive: bool = True, token2char: dict = {}):
@@ -392,12 +417,16 @@ class ASRModel(torch.nn.Module):
     def attention_rescoring_batch(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int,
                                   ctc_weight: float = 0.0, reverse_weight: float = 0.0,
                                   lm: Optional[torch.nn.Module] = None, lm_weight: float = 0.0,
-                                  use_graphs: Optional[bool] = None) -> List[List[int]]:
+                                  use_graphs: Optional[bool] = None, first_pass_lm: bool = False,
+                                  first_pass_lm_weight: Optional[float] = None, length_bonus: float = 0.0) -> List[List[int]]:
         """Batched form of attention_rescoring (the reference handles one utterance per call,
         asr_model.py:444): ONE encoder pass and ONE fused log-softmax top-k for the whole batch, the prefix
         recursion of every utterance on its own valid frames (one wave each on the device; OE_DEVICE_BEAM=0: native host
         code), then ONE bi-decoder pass over all B x beam hypotheses and the same score mix (asr_model.py:504-528).
-        use_graphs (default: OE_DECODE_GRAPHS, off): replay the two stages from HIP graphs cached per shape."""
+        use_graphs (default: OE_DECODE_GRAPHS, off): replay the two stages from HIP graphs cached per shape.
+        first_pass_lm: with an NgramLM and lm_weight > 0 the n-best lists come from the LM-fused search (ctc_lm_beam_search's
+        kernel, pruning by CTC + first_pass_lm_weight * LM + length_bonus * length; the weight defaults to lm_weight); the
+        rescoring itself is unchanged and takes the prefixes' plain CTC scores."""
         from openeat_amd import hip
         device = features.device
         B = features.shape[0]
@@ -406,10 +435,14 @@ class ASRModel(torch.nn.Module):
             raise IndexError("reverse_weight > 0 needs r_decoder_num_blocks > 0 (as in the reference)")
         on_device = DEVICE_BEAM and beam_size <= 16
         graphs = DECODE_GRAPHS if use_graphs is None else bool(use_graphs)
+        fuse = None
+        if first_pass_lm and isinstance(lm, NgramLM) and lm_weight > 0:
+            _require_fused_beam(lm, beam_size)
+            fuse = (lm, float(lm_weight if first_pass_lm_weight is None else first_pass_lm_weight), float(length_bonus))
         if on_device and graphs:
-            return self._rescoring_batch_graphs(features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight)
+            return self._rescoring_batch_graphs(features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight, fuse)
         if on_device:
-            encoder_out, encoder_mask, pre, plen, ctc_scores, bad = self._rescore_stage1(features, features_length, beam_size)
+            encoder_out, encoder_mask, pre, plen, ctc_scores, bad = self._rescore_stage1(features, features_length, beam_size, fuse)
             Lm = max(int(plen.max()), 1)                           # the one host sync of the n-best stage
             if int(bad):
                 raise RuntimeError("oe_ctc_prefix_beam: a prefix exceeded max_len")
@@ -439,15 +472,19 @@ class ASRModel(torch.nn.Module):
         return [list(nbest[b][best[b]][0]) for b in range(B)]
 
     # ---- the pieces of the batched rescoring (each of fixed shape given (B, T) resp. (B, T', L): capturable) --------------
-    def _rescore_stage1(self, features, features_length, beam_size):
+    def _rescore_stage1(self, features, features_length, beam_size, fuse=None):
         """Encoder, CTC projection, fused log-softmax top-k, prefix recursion - all on the device, no host sync.
         Returns encoder_out, encoder_mask, prefixes (R, T') int32, lengths (R) int32 (-1: the slot does not exist), CTC
-        scores (R) float64, status word."""
+        scores (R) float64, status word.  fuse = (NgramLM, weight, length bonus): the LM-fused recursion picks the prefixes."""
         from openeat_amd import hip
         encoder_out, encoder_mask, _ = self._encode(features, features_length)
         lens = encoder_mask.squeeze(1).sum(1)
         top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
-        pre, plen, ctc_scores, bad = hip.ctc_prefix_beam_device(top_p, top_i, lens.to(torch.int32), beam_size, raw=True)
+        if fuse is not None:
+            pre, plen, _, ctc_scores, _, bad = hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, fuse[0],
+                                                                             fuse[1], fuse[2], eos=True, raw=True)
+        else:
+            pre, plen, ctc_scores, bad = hip.ctc_prefix_beam_device(top_p, top_i, lens.to(torch.int32), beam_size, raw=True)
         R = pre.shape[0] * beam_size
         return encoder_out, encoder_mask, pre.view(R, -1), plen.view(R), ctc_scores.view(R), bad
 
@@ -505,7 +542,7 @@ class ASRModel(torch.nn.Module):
         score = score.masked_fill(missing, -float("inf"))         # (0 * -inf above would be nan: the slot is out whatever the weights)
         return score.view(B, beam_size).argmax(1)
 
-    def _rescoring_batch_graphs(self, features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight):
+    def _rescoring_batch_graphs(self, features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight, fuse=None):
         """The same two stages replayed from HIP graphs (decode is launch-bound: ~1500 small launches for 64 utterances):
         stage 1 keyed by the feature shape, stage 2 by the n-best length rounded up to a multiple of 16; between them the one
         host read of the longest hypothesis.  A shape is run eagerly the first time it is seen and captured for the next;
@@ -517,7 +554,9 @@ class ASRModel(torch.nn.Module):
         common.STATIC_SHAPES = True                                # label bookkeeping of fixed width: nothing reads a length on the host
         try:
             k1 = ("s1", tuple(features.shape), beam_size)
-            out1 = _graph_call(cache, k1, lambda f, fl: self._rescore_stage1(f, fl, beam_size), (features, features_length))
+            if fuse is not None:                                   # the fused recursion reads this model's tables and these weights
+                k1 = k1 + (id(fuse[0]), fuse[1], fuse[2], True)
+            out1 = _graph_call(cache, k1, lambda f, fl: self._rescore_stage1(f, fl, beam_size, fuse), (features, features_length))
             encoder_out, encoder_mask, pre, plen, ctc_scores, bad = out1
             Lm = max(int(plen.max()), 1)
             if int(bad):
