@@ -1,5 +1,7 @@
-// CTC prefix beam search on the device, one wavefront per utterance
-// (/root/reference/openeat/models/asr_model.py:359-396: the per-frame Python dict loop).
+// CTC prefix beam search on the device, one wavefront per utterance, plain and with n-gram LM shallow fusion: one kernel
+// source, template <bool LM>, two entry points (oe_ctc_prefix_beam, oe_ctc_prefix_beam_lm; semantics in
+// include/openeat_hip.h).
+// (the reference's openeat/models/asr_model.py:359-396: the per-frame Python dict loop).
 //
 // Same arithmetic and the same ordering as the reference and as the host implementation (beam_host.cpp, which stays as
 // the checker): python floats = doubles, log_add = max + log(sum exp(. - max)) accumulated in the order the reference
@@ -22,13 +24,40 @@
 // token appended) kept in a workspace.
 // Differences from the host version: exp / log are the device's double-precision routines (<= 1 ulp, not glibc's), so a
 // score can differ in its last bits.
+//
+// The fusion (LM = true) is this recursion with ONE change - the key that orders next_hyps before the cut to `beam` is
+//   total(p) = log_add(pb, pnb) + lm_weight * LM(p) + length_bonus * len(p)
+// instead of log_add(pb, pnb) - plus, at the end of the utterance, the optional </s> term and a stable re-sort of the
+// survivors by total.  Everything it adds sits under `if constexpr (LM)`; the pb / pnb arithmetic is the same statements
+// in both instantiations, so out_ctc is the same bits as the plain search's score wherever both keep the same prefixes,
+// and under zero weights the two searches are the same search.
+//
+// LM state.  LM(p) depends on the prefix only, so it is carried per current prefix, in LDS, next to pb / pnb:
+//   lm            float64, the terms of p's words added left to right;
+//   ent[j-1], bo[j-1], j = 1 .. order-1:  the entry number of the LAST j words of <s> p as an n-gram (-1: not listed, or
+//                 fewer than j words exist) and that n-gram's back-off.
+// The term of a word w after p then needs at most `order` INDEPENDENT probes: the unigram of w (an array read) and, for
+// every listed context j, the key (ent[j-1] << 32 | w) of the (j+1)-gram.  With K the length of the longest hit,
+//   term = bo[order-2] + ( .. + (bo[K-1] + logp_K))        over the LISTED contexts j = K .. order-1, shortest first,
+// which is the ARPA recursion unrolled; the hits are the next state.  This is exact under the one closure property the
+// reader guarantees (a listed n-gram's first k-1 words are listed: an unlisted context cannot start a listed n-gram).
+// Nothing is assumed about suffixes: a 3-gram may hit where the 2-gram of its last two words does not.
+//
+// What the fusion runs in parallel: the probes of all beam x beam extension candidates that are NEW prefixes (lane =
+// pair).  A "stay" entry and an extension that lands on a prefix already in the beam keep that prefix's lm and state and
+// probe nothing.  Candidates carry only the lm VALUE in registers; after the selection the <= beam winners that are new
+// prefixes redo their probes (one lane each) to write the state of the next frame.
+// Bound: latency.  The fusion adds two rounds of <= order-1 independent 16-byte gathers per frame into a table that does
+// not fit LDS.
 #include <math.h>
 #include "oe_common.h"
 #include "../../include/openeat_hip.h"
+#include "ngram_common.h"
 
 #define PB_MAXBEAM 16
 #define PB_MAXC ((PB_MAXBEAM * PB_MAXBEAM + 63) / 64)          // (token, hypothesis) pairs per lane
 #define PB_HASH_MUL 0x9E3779B97F4A7C15ull
+#define PB_H (NG_MAXORDER - 1)                                 // LM contexts kept per prefix
 
 __device__ __forceinline__ double pb_neg() { return -__builtin_huge_val(); }
 // log_add (common.py:198-206): max + log(sum of exp(. - max)) in argument order.  exp(0) = 1 and exp(-inf) = 0 exactly, so the
@@ -49,21 +78,69 @@ __device__ __forceinline__ double pb_log_add3(double a, double b, double c) {
     const double m = fmax(a, fmax(b, c));
     return m + log(pb_term(a, m) + pb_term(b, m) + pb_term(c, m));
 }
-__device__ __forceinline__ double pb_shfl_xor(double v, int o) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, o, 64);
-    hi = __shfl_xor(hi, o, 64);
-    return __hiloint2double(hi, lo);
+// (ctc + lm_weight * lm) + length_bonus * len with every product and sum rounded on its own, as a host float64 expression
+// is: a fused multiply-add would move a total by an ulp and with it the order of two entries that tie exactly.
+__device__ __forceinline__ double pb_total(double ctc, double lm, int len, double lm_weight, double length_bonus) {
+#pragma clang fp contract(off)
+    const double a = lm_weight * lm;
+    const double c = length_bonus * (double)len;
+    return (ctc + a) + c;
 }
 
-struct PbHyp {          // one entry of next_hyps
+// log10 p(w | the prefix whose state is ent / bo); ent_out / bo_out (or null): the state of prefix + w
+__device__ __forceinline__ double pb_extend(const NgModel& m, const int* ent, const float* bo, int w, int* ent_out, float* bo_out) {
+    const int H = m.order - 1;
+    const float2 u = m.unigrams[w];
+    int ce[PB_H], he[PB_H];
+    float cb[PB_H], hl[PB_H], hb[PB_H];
+#pragma unroll
+    for (int j = 0; j < PB_H; ++j) {
+        ce[j] = j < H ? ent[j] : -1;
+        cb[j] = j < H ? bo[j] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < PB_H; ++j) {                               // the (j+2)-gram: context of j+1 words, then w
+        he[j] = -1; hl[j] = 0.f; hb[j] = 0.f;
+        if (ce[j] >= 0) {
+            const unsigned long long key = ((unsigned long long)(unsigned)ce[j] << 32) | (unsigned)w;
+            const long slot = ng_find(m.table, m.mask, m.max_probe, key, hl[j], hb[j]);
+            if (slot >= 0) he[j] = m.n_words + (int)slot;
+        }
+    }
+    int K = 1;
+    float lp = u.x;
+#pragma unroll
+    for (int j = 0; j < PB_H; ++j)
+        if (he[j] >= 0) { K = j + 2; lp = hl[j]; }
+    double term = (double)lp;
+#pragma unroll
+    for (int j = 0; j < PB_H; ++j)
+        if (j + 1 >= K && ce[j] >= 0) term = (double)cb[j] + term;
+    if (ent_out) {
+        ent_out[0] = w; bo_out[0] = u.y;
+#pragma unroll
+        for (int j = 1; j < PB_H; ++j) { ent_out[j] = he[j - 1]; bo_out[j] = hb[j - 1]; }
+    }
+    return term;
+}
+
+struct PbHyp {          // one entry of next_hyps; score: the pruning key; lm: LM only
     unsigned long long key;
-    double pb, pnb, score;
+    double pb, pnb, lm, score;
     int len, last, parent, tok, order;
 };
 
+struct PbLmArgs {       // what the fusion takes on top of the plain search (all zero for LM = false)
+    NgModel m;
+    double lm_weight, length_bonus;
+    int eos;
+    double* __restrict__ out_ctc;
+    double* __restrict__ out_lm;
+};
+
+template <bool LM>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ topk_logp, const long long* __restrict__ topk_idx,
-                                                             int Tmax, const int* __restrict__ lens, int beam, int max_len,
+                                                             int Tmax, const int* __restrict__ lens, int beam, int max_len, PbLmArgs la,
                                                              int* __restrict__ hist, int* __restrict__ out_prefix,
                                                              int* __restrict__ out_len, double* __restrict__ out_score,
                                                              int* __restrict__ status) {
@@ -77,20 +154,35 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
     __shared__ unsigned long long nx_key[PB_MAXBEAM];
     __shared__ double nx_pb[PB_MAXBEAM], nx_pnb[PB_MAXBEAM];
     __shared__ int nx_len[PB_MAXBEAM], nx_last[PB_MAXBEAM];
+    // LM only (never referenced, so not allocated, for LM = false)
+    __shared__ double cur_lm[PB_MAXBEAM], nx_lm[PB_MAXBEAM], fin_total[PB_MAXBEAM];
+    __shared__ int cur_ent[PB_MAXBEAM][PB_H], nx_ent[PB_MAXBEAM][PB_H];
+    __shared__ float cur_bo[PB_MAXBEAM][PB_H], nx_bo[PB_MAXBEAM][PB_H];
+    __shared__ int tk_w[PB_MAXBEAM], nx_parent[PB_MAXBEAM], nx_tok[PB_MAXBEAM];
 
     const int b = blockIdx.x, lane = threadIdx.x;
     const int T = min(lens ? lens[b] : Tmax, Tmax);
     const double NEG = pb_neg();
     int ncur = 1;
-    if (lane == 0) { cur_key[0] = 0; cur_pb[0] = 0.0; cur_pnb[0] = NEG; cur_len[0] = 0; cur_last[0] = -1; }
+    if (lane == 0) {
+        cur_key[0] = 0; cur_pb[0] = 0.0; cur_pnb[0] = NEG; cur_len[0] = 0; cur_last[0] = -1;
+        if constexpr (LM) {
+            cur_lm[0] = 0.0;
+            cur_ent[0][0] = la.m.bos_word; cur_bo[0][0] = la.m.unigrams[la.m.bos_word].y;          // the context <s>
+#pragma unroll
+            for (int j = 1; j < PB_H; ++j) { cur_ent[0][j] = -1; cur_bo[0][j] = 0.f; }
+        }
+    }
     __syncthreads();
     int* hist_b = hist + (long)b * Tmax * beam * 2;
 
     for (int t = 0; t < T; ++t) {
         if (lane < beam) {
             const long o = ((long)b * Tmax + t) * beam + lane;
+            const int s = (int)topk_idx[o];
             tk_ps[lane] = (double)topk_logp[o];
-            tk_s[lane] = (int)topk_idx[o];
+            tk_s[lane] = s;
+            if constexpr (LM) tk_w[lane] = ng_word(la.m, s);
         }
         if (lane < ncur) con_has[lane] = 0;
         __syncthreads();
@@ -124,6 +216,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                         cand[c].pb = NEG;
                         cand[c].pnb = rep ? a : pb_log_add3(NEG, a, bb);
                         cand[c].order = 2 * p + 1;
+                        if constexpr (LM) cand[c].lm = cur_lm[h] + pb_extend(la.m, cur_ent[h], cur_bo[h], tk_w[j], nullptr, nullptr);
                     }
                 }
             }
@@ -159,11 +252,15 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                 alive[PB_MAXC] = true;
                 PbHyp& e = cand[PB_MAXC];
                 e.key = cur_key[n]; e.len = cur_len[n]; e.last = last; e.parent = n; e.tok = -1; e.pb = npb; e.pnb = npnb; e.order = order;
+                if constexpr (LM) e.lm = cur_lm[n];
             }
         }
 #pragma unroll
         for (int c = 0; c <= PB_MAXC; ++c)
-            if (alive[c]) cand[c].score = pb_log_add2(cand[c].pb, cand[c].pnb);
+            if (alive[c]) {
+                cand[c].score = pb_log_add2(cand[c].pb, cand[c].pnb);
+                if constexpr (LM) cand[c].score = pb_total(cand[c].score, cand[c].lm, cand[c].len, la.lm_weight, la.length_bonus);
+            }
 
         // ---- the best `beam` entries by (score descending, first touch ascending)
         int nsel = 0;
@@ -177,7 +274,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             int wo = bo;                                      // lanes without a candidate carry (NEG, INT_MAX)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
-                const double os = pb_shfl_xor(ws, o);
+                const double os = oe_shfl_xor_f64(ws, o);
                 const int oo = __shfl_xor(wo, o, 64);
                 if (oo != 0x7fffffff && (wo == 0x7fffffff || os > ws || (os == ws && oo < wo))) { ws = os; wo = oo; }
             }
@@ -187,6 +284,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                 for (int c = 0; c <= PB_MAXC; ++c)
                     if (c == bc) {
                         nx_key[r] = cand[c].key; nx_pb[r] = cand[c].pb; nx_pnb[r] = cand[c].pnb; nx_len[r] = cand[c].len; nx_last[r] = cand[c].last;
+                        if constexpr (LM) { nx_lm[r] = cand[c].lm; nx_parent[r] = cand[c].parent; nx_tok[r] = cand[c].tok; }
                         hist_b[((long)t * beam + r) * 2] = cand[c].parent;
                         hist_b[((long)t * beam + r) * 2 + 1] = cand[c].tok;
                         alive[c] = false;
@@ -195,17 +293,65 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             nsel = r + 1;
         }
         __syncthreads();
-        if (lane < nsel) { cur_key[lane] = nx_key[lane]; cur_pb[lane] = nx_pb[lane]; cur_pnb[lane] = nx_pnb[lane]; cur_len[lane] = nx_len[lane]; cur_last[lane] = nx_last[lane]; }
+        if constexpr (LM) {
+            // ---- the winners' LM state: a new prefix redoes its probes, any other entry keeps its prefix's state
+            if (lane < nsel) {
+                const int par = nx_parent[lane], tok = nx_tok[lane];
+                if (tok >= 0) {
+                    pb_extend(la.m, cur_ent[par], cur_bo[par], ng_word(la.m, tok), nx_ent[lane], nx_bo[lane]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < PB_H; ++j) { nx_ent[lane][j] = cur_ent[par][j]; nx_bo[lane][j] = cur_bo[par][j]; }
+                }
+            }
+            __syncthreads();
+        }
+        if (lane < nsel) {
+            cur_key[lane] = nx_key[lane]; cur_pb[lane] = nx_pb[lane]; cur_pnb[lane] = nx_pnb[lane]; cur_len[lane] = nx_len[lane];
+            cur_last[lane] = nx_last[lane];
+            if constexpr (LM) {
+                cur_lm[lane] = nx_lm[lane];
+#pragma unroll
+                for (int j = 0; j < PB_H; ++j) { cur_ent[lane][j] = nx_ent[lane][j]; cur_bo[lane][j] = nx_bo[lane][j]; }
+            }
+        }
         ncur = nsel;
+        __syncthreads();
+    }
+
+    // ---- LM, end of the utterance: the </s> term, then the survivors stably re-sorted by total
+    double lm = 0.0, ctc = NEG, total = NEG;
+    if constexpr (LM) {
+        if (lane < ncur) {
+            lm = cur_lm[lane];
+            if (la.eos) lm = lm + pb_extend(la.m, cur_ent[lane], cur_bo[lane], la.m.eos_word, nullptr, nullptr);
+            ctc = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
+            total = pb_total(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus);
+            fin_total[lane] = total;
+        }
         __syncthreads();
     }
 
     // ---- results: scores, lengths, tokens by walking the back-pointers
     if (lane < beam) {
-        const long o = (long)b * beam + lane;
         if (lane < ncur) {
+            int rank = lane;
+            if constexpr (LM) {
+                rank = 0;
+                for (int i = 0; i < ncur; ++i) {
+                    const double ti = fin_total[i];
+                    if (ti > total || (ti == total && i < lane)) ++rank;
+                }
+            }
+            const long o = (long)b * beam + rank;
             const int len = cur_len[lane];
-            out_score[o] = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
+            if constexpr (LM) {
+                out_score[o] = total;
+                la.out_ctc[o] = ctc;
+                la.out_lm[o] = lm;
+            } else {
+                out_score[o] = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
+            }
             out_len[o] = len;
             if (len > max_len) { atomicExch(status, 1); return; }
             int slot = lane, pos = len - 1;
@@ -215,25 +361,60 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                 slot = parent;
             }
         } else {
+            const long o = (long)b * beam + lane;
             out_score[o] = NEG;
+            if constexpr (LM) { la.out_ctc[o] = NEG; la.out_lm[o] = NEG; }
             out_len[o] = -1;
         }
     }
 }
 
-extern "C" size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam) {
-    return ((size_t)B * (size_t)max(Tmax, 1) * (size_t)beam * 2 + 1) * sizeof(int);
+// back-pointer words of the workspace; one status word follows them
+static size_t pb_hist_words(int B, int Tmax, int beam) { return (size_t)B * (size_t)max(Tmax, 1) * (size_t)beam * 2; }
+
+extern "C" size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
+extern "C" size_t oe_ctc_prefix_beam_lm_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
+
+// fn: the entry point, for its messages
+static int pb_check_shape(const char* fn, int B, int Tmax, int max_len, int beam) {
+    OE_REQUIRE(B > 0 && Tmax >= 0 && max_len >= 0, "%s: bad shape B=%d Tmax=%d max_len=%d", fn, B, Tmax, max_len);
+    OE_REQUIRE(beam >= 1 && beam <= PB_MAXBEAM, "%s: beam must be 1..%d (got %d)", fn, PB_MAXBEAM, beam);
+    return 0;
+}
+
+template <bool LM>
+static int pb_launch(const char* name, const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
+                     int max_len, const PbLmArgs& la, void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream) {
+    int* hist = (int*)workspace;
+    int* status = hist + pb_hist_words(B, Tmax, beam);            // the caller zeroes this word and reads it back
+    hipLaunchKernelGGL(ctc_prefix_beam_kernel<LM>, dim3(B), dim3(64), 0, (hipStream_t)stream, topk_logp, topk_idx, Tmax, lens, beam,
+                       max_len, la, hist, out_prefix, out_len, out_score, status);
+    OE_LAUNCH_CHECK(name);
+    return 0;
 }
 
 extern "C" int oe_ctc_prefix_beam(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
                                   int max_len, void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream) {
     OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score, "oe_ctc_prefix_beam: null pointer");
-    OE_REQUIRE(B > 0 && Tmax >= 0 && max_len >= 0, "oe_ctc_prefix_beam: bad shape B=%d Tmax=%d max_len=%d", B, Tmax, max_len);
-    OE_REQUIRE(beam >= 1 && beam <= PB_MAXBEAM, "oe_ctc_prefix_beam: beam must be 1..%d (got %d)", PB_MAXBEAM, beam);
-    int* hist = (int*)workspace;
-    int* status = hist + (size_t)B * (size_t)max(Tmax, 1) * (size_t)beam * 2;     // the caller zeroes this word and reads it back
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, topk_logp, topk_idx, Tmax, lens, beam, max_len,
-                       hist, out_prefix, out_len, out_score, status);
-    OE_LAUNCH_CHECK("ctc_prefix_beam");
-    return 0;
+    if (pb_check_shape("oe_ctc_prefix_beam", B, Tmax, max_len, beam)) return -1;
+    return pb_launch<false>("ctc_prefix_beam", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, PbLmArgs{}, workspace, out_prefix,
+                            out_len, out_score, stream);
+}
+
+extern "C" int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
+                                     int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
+                                     int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V,
+                                     double lm_weight, double length_bonus, int eos, void* workspace, int* out_prefix, int* out_len,
+                                     double* out_score, double* out_ctc, double* out_lm, void* stream) {
+    const char* fn = "oe_ctc_prefix_beam_lm";
+    OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score && out_ctc && out_lm, "%s: null pointer", fn);
+    OE_REQUIRE(unigrams && table && tok2word, "%s: null pointer (model)", fn);
+    if (pb_check_shape(fn, B, Tmax, max_len, beam)) return -1;
+    PbLmArgs la{};
+    if (ng_model_args(fn, unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &la.m)) return -1;
+    OE_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", fn, V);
+    OE_REQUIRE(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight and length_bonus must be finite", fn);
+    la.lm_weight = lm_weight; la.length_bonus = length_bonus; la.eos = eos; la.out_ctc = out_ctc; la.out_lm = out_lm;
+    return pb_launch<true>("ctc_prefix_beam_lm", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix, out_len,
+                           out_score, stream);
 }

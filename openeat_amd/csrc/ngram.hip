@@ -31,20 +31,9 @@
 #define NG_TILE 64
 #define NG_COLS (NG_TILE + NG_MAXORDER - 1)
 
-__device__ __forceinline__ double ng_shfl_xor(double v, int o) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, o, 64);
-    hi = __shfl_xor(hi, o, 64);
-    return __hiloint2double(hi, lo);
-}
-
-__global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restrict__ unigrams, int n_words,
-                                                         const uint4* __restrict__ table, unsigned long long mask, int max_probe,
-                                                         int order, int bos_word, int eos_word, int unk_word,
-                                                         const int* __restrict__ tok2word, int V, const int* __restrict__ tokens,
-                                                         long ld, const int* __restrict__ lens, int bos, int eos,
-                                                         double* __restrict__ score, double* __restrict__ tok_logp,
-                                                         int* __restrict__ tok_order) {
+__global__ __launch_bounds__(64) void ngram_score_kernel(NgModel m, const int* __restrict__ tokens, long ld,
+                                                         const int* __restrict__ lens, int bos, int eos, double* __restrict__ score,
+                                                         double* __restrict__ tok_logp, int* __restrict__ tok_order) {
     __shared__ int wd[NG_COLS];                                  // word ids of positions base .. base + 63 + (order-1)
     __shared__ int found[NG_COLS];                               // column c = start position base - (NG_MAXORDER-1) + c
     __shared__ float lp[NG_MAXORDER][NG_COLS], bo[NG_MAXORDER][NG_COLS];
@@ -69,12 +58,9 @@ __global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restric
             const int q = base + c;
             int w = -1;
             if (q < P) {
-                if (q < off) w = bos_word;
-                else if (q - off < len) {
-                    const int t = tk[q - off];
-                    w = (t >= 0 && t < V) ? tok2word[t] : unk_word;
-                    if (w < 0 || w >= n_words) w = unk_word;
-                } else w = eos_word;
+                if (q < off) w = m.bos_word;
+                else if (q - off < len) w = ng_word(m, tk[q - off]);
+                else w = m.eos_word;
             }
             wd[c] = w;
         }
@@ -85,17 +71,17 @@ __global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restric
             int nf = 0;
             if (s < P) {
                 long e = wd[lane];
-                const float2 u = unigrams[e];
+                const float2 u = m.unigrams[e];
                 lp[0][H + lane] = u.x; bo[0][H + lane] = u.y;
                 nf = 1;
-                for (int k = 2; k <= order; ++k) {
+                for (int k = 2; k <= m.order; ++k) {
                     if (s + k - 1 >= P) break;
                     const unsigned long long key = ((unsigned long long)e << 32) | (unsigned)wd[lane + k - 1];
                     float a = 0.f, b = 0.f;
-                    const long slot = ng_find(table, mask, max_probe, key, a, b);
+                    const long slot = ng_find(m.table, m.mask, m.max_probe, key, a, b);
                     if (slot < 0) break;
                     lp[k - 1][H + lane] = a; bo[k - 1][H + lane] = b;
-                    e = (long)n_words + slot;
+                    e = (long)m.n_words + slot;
                     nf = k;
                 }
             }
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restric
             const int i = base + lane;
             if (i >= off && i < P) {
                 double term = 0.0;
-                int k = min(order, i + 1);
+                int k = min(m.order, i + 1);
                 for (; k > 1; --k) {
                     const int c = H + lane - (k - 1);            // chain that starts at i - k + 1
                     const int nf = found[c];
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(64) void ngram_score_kernel(const float2* __restric
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += ng_shfl_xor(acc, o);
+    for (int o = 32; o > 0; o >>= 1) acc += oe_shfl_xor_f64(acc, o);
     if (lane == 0) score[r] = acc;
 }
 
@@ -147,17 +133,13 @@ extern "C" int oe_ngram_score(const float* unigrams, int n_words, const void* ta
                               const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order,
                               void* stream) {
     OE_REQUIRE(unigrams && table && tok2word && tokens && lens && score, "oe_ngram_score: null pointer");
-    OE_REQUIRE(order >= 1 && order <= NG_MAXORDER, "oe_ngram_score: order must be 1..%d (got %d)", NG_MAXORDER, order);
-    OE_REQUIRE(capacity >= 2 && (capacity & (capacity - 1)) == 0, "oe_ngram_score: capacity must be a power of two >= 2 (got %ld)", capacity);
-    OE_REQUIRE(max_probe >= 0 && max_probe < capacity, "oe_ngram_score: bad max_probe %d", max_probe);
-    OE_REQUIRE(n_words > 0 && (long)n_words + capacity < 0x7fffffffL, "oe_ngram_score: n_words + capacity must stay below 2^31");
-    OE_REQUIRE(bos_word >= 0 && bos_word < n_words && eos_word >= 0 && eos_word < n_words && unk_word >= 0 && unk_word < n_words,
-               "oe_ngram_score: <s> / </s> / <unk> ids outside the vocabulary");
+    NgModel m;
+    if (ng_model_args("oe_ngram_score", unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &m))
+        return -1;
     OE_REQUIRE(R >= 0 && V > 0 && ld >= 0, "oe_ngram_score: bad shape R=%d V=%d ld=%ld", R, V, ld);
     if (R == 0) return 0;
-    hipLaunchKernelGGL(ngram_score_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, (const float2*)unigrams, n_words,
-                       (const uint4*)table, (unsigned long long)(capacity - 1), max_probe, order, bos_word, eos_word, unk_word,
-                       tok2word, V, tokens, ld, lens, bos, eos, score, tok_logp, tok_order);
+    hipLaunchKernelGGL(ngram_score_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, m, tokens, ld, lens, bos, eos, score, tok_logp,
+                       tok_order);
     OE_LAUNCH_CHECK("ngram_score");
     return 0;
 }

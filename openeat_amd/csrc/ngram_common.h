@@ -1,5 +1,5 @@
-// The n-gram table's slot and its exact-key lookup, shared by the kernels that read an NgramLM on the device
-// (ngram.hip: scores of finished hypotheses; beam_lm.hip: the LM state of every prefix inside the beam search).
+// The n-gram model's arguments, the table's slot and its exact-key lookup, shared by the kernels that read an NgramLM on the
+// device (ngram.hip: scores of finished hypotheses; beam.hip: the LM state of every prefix inside the fused beam search).
 // Layout and key chaining: include/openeat_hip.h (oe_ngram_score) and openeat_amd/models/ngram_lm.py.
 #pragma once
 #include "oe_common.h"
@@ -31,4 +31,36 @@ __device__ __forceinline__ long ng_find(const uint4* __restrict__ table, unsigne
         slot = (slot + 1) & mask;
     }
     return -1;
+}
+
+struct NgModel {           // the arguments of oe_ngram_score that describe the model
+    const float2* unigrams;
+    const uint4* table;
+    const int* tok2word;
+    unsigned long long mask;   // capacity - 1
+    int n_words, max_probe, order, bos_word, eos_word, unk_word, V;
+};
+
+// word id of a token: <unk> for a token outside [0, V) and for one the map sends outside the vocabulary
+__device__ __forceinline__ int ng_word(const NgModel& m, int tok) {
+    int w = (tok >= 0 && tok < m.V) ? m.tok2word[tok] : m.unk_word;
+    if (w < 0 || w >= m.n_words) w = m.unk_word;
+    return w;
+}
+
+// Host: the checks every entry point makes on the model arguments (fn: its name, for the messages; pointers and V are the
+// caller's to check), then the arguments as the kernels take them.
+static inline int ng_model_args(const char* fn, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
+                                int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, NgModel* m) {
+    OE_REQUIRE(order >= 1 && order <= NG_MAXORDER, "%s: order must be 1..%d (got %d)", fn, NG_MAXORDER, order);
+    OE_REQUIRE(capacity >= 2 && (capacity & (capacity - 1)) == 0, "%s: capacity must be a power of two >= 2 (got %ld)", fn, capacity);
+    OE_REQUIRE(max_probe >= 0 && max_probe < capacity, "%s: bad max_probe %d", fn, max_probe);
+    OE_REQUIRE(n_words > 0 && (long)n_words + capacity < 0x7fffffffL, "%s: n_words + capacity must stay below 2^31", fn);
+    OE_REQUIRE(bos_word >= 0 && bos_word < n_words && eos_word >= 0 && eos_word < n_words && unk_word >= 0 && unk_word < n_words,
+               "%s: <s> / </s> / <unk> ids outside the vocabulary", fn);
+    m->unigrams = (const float2*)unigrams; m->table = (const uint4*)table; m->tok2word = tok2word;
+    m->mask = (unsigned long long)(capacity - 1);
+    m->n_words = n_words; m->max_probe = max_probe; m->order = order;
+    m->bos_word = bos_word; m->eos_word = eos_word; m->unk_word = unk_word; m->V = V;
+    return 0;
 }

@@ -41,6 +41,13 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// a double from the lane `o` away (xor), as two 32-bit shuffles
+__device__ __forceinline__ double oe_shfl_xor_f64(double v, int o) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_xor(lo, o, 64);
+    hi = __shfl_xor(hi, o, 64);
+    return __hiloint2double(hi, lo);
+}
 // (max, sum-of-exp) pair merge for online log-sum-exp
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
     float mn = fmaxf(m, m2);

@@ -521,31 +521,51 @@ def attention_bwd(a: AttnArgs):
     check(lib().oe_attention_bwd(C.byref(a), stream()), "oe_attention_bwd")
 
 
+def _prefix_beam_buffers(name, top_logp, top_idx, beam, n_scores):
+    """The argument check and the allocations the two device prefix searches share (name: oe_<name> is the entry point) ->
+    contiguous inputs, B, T, max_len, workspace (status word zeroed), prefixes (B, beam, max_len) int32, lengths (B, beam)
+    int32, n_scores x (B, beam) float64."""
+    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
+        raise TypeError(f"{name}_device: float32 / int64 CUDA tensors required")
+    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
+    B, T = top_logp.shape[0], top_logp.shape[1]
+    ml = max(T, 1)
+    dev = top_logp.device
+    ws = torch.empty(getattr(lib(), f"oe_{name}_workspace_bytes")(B, T, beam) // 4, dtype=torch.int32, device=dev)
+    ws[-1:].zero_()
+    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
+    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    scores = [torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(n_scores)]
+    return top_logp, top_idx, B, T, ml, ws, prefixes, plen, scores
+
+
+def check_prefix_beam_status(bad, name: str = "oe_ctc_prefix_beam"):
+    """bad: the status word of a device prefix search, read after the stream has drained."""
+    if int(bad):
+        raise RuntimeError(f"{name}: a prefix exceeded max_len")
+
+
+def _nbest_lists(prefixes, plen, *scores):
+    """(B, beam, max_len) prefixes, (B, beam) lengths (-1: no entry) and score arrays, tensors or numpy -> per utterance
+    [(prefix tuple, score, ...)]."""
+    prefixes, plen, *scores = (a.cpu().numpy() if isinstance(a, torch.Tensor) else a for a in (prefixes, plen, *scores))
+    B, beam = plen.shape
+    return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), *(float(s[b, i]) for s in scores)) for i in range(beam) if plen[b, i] >= 0]
+            for b in range(B)]
+
+
 def ctc_prefix_beam_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, raw: bool = False):
     """top_logp (B, T, beam) float32 / top_idx (B, T, beam) int64 CUDA tensors (ops.topk_rows), lens (B) int32 CUDA or None ->
     per utterance [(prefix tuple, score)], as ctc_prefix_beam_host_batch returns them.  One kernel, one wave per
     utterance; one device-to-host copy of the n-best lists.  raw=True: no copy at all - the device tensors
     (prefixes (B, beam, T) int32, lengths (B, beam) int32 with -1 for missing entries, scores (B, beam) float64) and a
     status word tensor the caller checks after its own synchronisation."""
-    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
-        raise TypeError("ctc_prefix_beam_device: float32 / int64 CUDA tensors required")
-    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
-    B, T = top_logp.shape[0], top_logp.shape[1]
-    ml = max(T, 1)
-    dev = top_logp.device
-    ws = torch.empty(lib().oe_ctc_prefix_beam_workspace_bytes(B, T, beam) // 4, dtype=torch.int32, device=dev)
-    ws[-1:].zero_()
-    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
-    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, beam, dtype=torch.float64, device=dev)
+    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (scores,) = _prefix_beam_buffers("ctc_prefix_beam", top_logp, top_idx, beam, 1)
     call("oe_ctc_prefix_beam", top_logp, top_idx, B, T, lens, beam, ml, ws, prefixes, plen, scores)
     if raw:
         return prefixes, plen, scores, ws[-1:]
-    prefixes, plen, scores, bad = prefixes.cpu().numpy(), plen.cpu().numpy(), scores.cpu().numpy(), int(ws[-1])
-    if bad:
-        raise RuntimeError("oe_ctc_prefix_beam: a prefix exceeded max_len")
-    return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), float(scores[b, i])) for i in range(beam) if plen[b, i] >= 0]
-            for b in range(B)]
+    check_prefix_beam_status(ws[-1])                               # the read drains the stream
+    return _nbest_lists(prefixes, plen, scores)
 
 
 def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, lm,
@@ -555,29 +575,15 @@ def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, len
     [(prefix tuple, total, ctc, lm)] sorted by total.  raw=True: no copy at all - the device tensors (prefixes (B, beam, T)
     int32, lengths (B, beam) int32 with -1 for missing entries, total / ctc / lm (B, beam) float64, -inf where missing) and
     the status word tensor the caller checks after its own synchronisation."""
-    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
-        raise TypeError("ctc_prefix_beam_lm_device: float32 / int64 CUDA tensors required")
-    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
-    B, T = top_logp.shape[0], top_logp.shape[1]
-    ml = max(T, 1)
-    dev = top_logp.device
-    uni, table, tok2word = lm.device_tables(dev)
-    ws = torch.empty(lib().oe_ctc_prefix_beam_lm_workspace_bytes(B, T, beam) // 4, dtype=torch.int32, device=dev)
-    ws[-1:].zero_()
-    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
-    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    total, ctc, lms = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(3))
+    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (total, ctc, lms) = _prefix_beam_buffers("ctc_prefix_beam_lm", top_logp, top_idx, beam, 3)
+    uni, table, tok2word = lm.device_tables(top_logp.device)
     call("oe_ctc_prefix_beam_lm", top_logp, top_idx, B, T, lens, beam, ml, uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order,
          lm.bos_word, lm.eos_word, lm.unk_word, tok2word, int(tok2word.shape[0]), float(lm_weight), float(length_bonus),
          int(bool(eos)), ws, prefixes, plen, total, ctc, lms)
     if raw:
         return prefixes, plen, total, ctc, lms, ws[-1:]
-    prefixes, plen, bad = prefixes.cpu().numpy(), plen.cpu().numpy(), int(ws[-1])
-    total, ctc, lms = total.cpu().numpy(), ctc.cpu().numpy(), lms.cpu().numpy()
-    if bad:
-        raise RuntimeError("oe_ctc_prefix_beam_lm: a prefix exceeded max_len")
-    return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), float(total[b, i]), float(ctc[b, i]), float(lms[b, i]))
-             for i in range(beam) if plen[b, i] >= 0] for b in range(B)]
+    check_prefix_beam_status(ws[-1], "oe_ctc_prefix_beam_lm")
+    return _nbest_lists(prefixes, plen, total, ctc, lms)
 
 
 def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, lens, beam: int, n_threads: int = 0):
@@ -595,8 +601,7 @@ def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, le
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     check(lib().oe_ctc_prefix_beam_host_batch(vp(lp), vp(ix), B, T, vp(ln), beam, ml, vp(prefixes), vp(plen), vp(scores), n_threads),
           "oe_ctc_prefix_beam_host_batch")
-    return [[(tuple(prefixes[b, i, : plen[b, i]].tolist()), float(scores[b, i])) for i in range(beam) if plen[b, i] >= 0]
-            for b in range(B)]
+    return _nbest_lists(prefixes, plen, scores)
 
 
 def ctc_prefix_beam_host(top_logp: torch.Tensor, top_idx: torch.Tensor, beam: int):

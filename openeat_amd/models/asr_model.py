@@ -34,7 +34,7 @@ ATT_INPUTS_KERNEL = os.environ.get("OE_ATT_INPUTS_KERNEL", "1") != "0"      # de
 
 
 def _require_fused_beam(lm, beam_size):
-    """The LM-fused prefix search exists on the device only (beam_lm.hip): an NgramLM, the device beam, beam <= 16."""
+    """The LM-fused prefix search exists on the device only (beam.hip): an NgramLM, the device beam, beam <= 16."""
     if not isinstance(lm, NgramLM):
         raise ValueError(f"the LM-fused CTC beam search needs an NgramLM (got {type(lm).__name__})")
     if not DEVICE_BEAM:
@@ -444,8 +444,7 @@ class ASRModel(torch.nn.Module):
         if on_device:
             encoder_out, encoder_mask, pre, plen, ctc_scores, bad = self._rescore_stage1(features, features_length, beam_size, fuse)
             Lm = max(int(plen.max()), 1)                           # the one host sync of the n-best stage
-            if int(bad):
-                raise RuntimeError("oe_ctc_prefix_beam: a prefix exceeded max_len")
+            hip.check_prefix_beam_status(bad)
             toks, n, mean_len = self._rescore_stage2(encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight,
                                                      reverse_weight, lm, lm_weight)
             self.last_nbest_mean_len = float(mean_len)
@@ -547,6 +546,7 @@ class ASRModel(torch.nn.Module):
         stage 1 keyed by the feature shape, stage 2 by the n-best length rounded up to a multiple of 16; between them the one
         host read of the longest hypothesis.  A shape is run eagerly the first time it is seen and captured for the next;
         a stage that cannot be captured keeps running eagerly.  At most DECODE_GRAPH_SLOTS graphs per stage are kept."""
+        from openeat_amd import hip
         from openeat_amd.utils import common
         B = features.shape[0]
         cache = self.__dict__.setdefault("_decode_graphs", {})
@@ -559,8 +559,7 @@ class ASRModel(torch.nn.Module):
             out1 = _graph_call(cache, k1, lambda f, fl: self._rescore_stage1(f, fl, beam_size, fuse), (features, features_length))
             encoder_out, encoder_mask, pre, plen, ctc_scores, bad = out1
             Lm = max(int(plen.max()), 1)
-            if int(bad):
-                raise RuntimeError("oe_ctc_prefix_beam: a prefix exceeded max_len")
+            hip.check_prefix_beam_status(bad)
             Lb = min(-(-Lm // 16) * 16, pre.shape[1])
             k2 = ("s2", tuple(encoder_out.shape), beam_size, Lb, float(ctc_weight), float(reverse_weight), id(lm), float(lm_weight))
             toks, n, mean_len = _graph_call(

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The LM-fused CTC prefix beam search (oe_ctc_prefix_beam_lm) against the plain one (oe_ctc_prefix_beam) on the same top-k
-(GPU box).
+"""The LM-fused CTC prefix beam search (oe_ctc_prefix_beam_lm) against the plain one (oe_ctc_prefix_beam) on the same top-k:
+the two instantiations of beam.hip's kernel (GPU box).
 
   python tools/lm_beam_bench.py           # 64 utterances x 250 frames, beam 10, synthetic n-gram models of order 3 and 5
 
