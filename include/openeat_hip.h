@@ -742,6 +742,56 @@ int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int
                           double length_bonus, int eos, void* workspace, int* out_prefix, int* out_len, double* out_score,
                           double* out_ctc, double* out_lm, void* stream);
 
+/* CTC prefix beam search with hotword (contextual) biasing on the device, one wavefront per utterance, with or without the
+ * n-gram LM.  These are the semantics every layer refers to.
+ * A context graph is a set of distinct phrases q, each a sequence of 1..32 token ids in 1..V-1 (never the blank) with a
+ * float32 score s(q), and one float32 per-token partial credit c >= 0; by default s(q) = c * len(q) in float32.  For a
+ * token prefix p:
+ *   hits(p) = the sum of s(q) over every occurrence of every phrase in p, an occurrence being a pair (i, q) with
+ *             p[i-len(q):i] == q, 1 <= i <= len(p); overlapping and nested occurrences all count.  The float32 values are
+ *             added in float64 in order of increasing i, within one i the longest phrase first.
+ *   k(p)    = the largest k <= len(p) such that the last k tokens of p are a PROPER prefix of some phrase (strictly
+ *             shorter than it); 0 if there is none.
+ *   bias(p) = hits(p) + (double)c * k(p) during the search; at the end of the utterance, with `final` set, the pending
+ *             credit is dropped: bias(p) = hits(p).
+ * Partial credit keeps a half-spoken hotword in the beam; it is taken back when the phrase fails and at the end of the audio.
+ * The search is oe_ctc_prefix_beam_lm's with one more summand, products and sums each rounded on their own:
+ *   total(p) = ((log_add(pb, pnb) + lm_weight * LM(p)) + length_bonus * len(p)) + bias(p)
+ *   without an LM (unigrams == NULL):  total(p) = (log_add(pb, pnb) + length_bonus * len(p)) + bias(p).
+ * The pb / pnb updates, the visiting order, the first-touch stamps and the stable descending sort are unchanged.  bias(p)
+ * depends on the prefix only: two routes that merge into one prefix carry the same value and the same automaton state.
+ * End of the utterance: (1) the </s> LM term if an LM is given and eos; (2) the pending credit dropped if final; (3) the
+ * survivors stably re-sorted by total.  An utterance of zero frames yields the one empty prefix with bias 0.
+ * Identities: with an empty graph, and with one whose scores and c are all zero, the n-best lists, their order, out_ctc,
+ *   out_lm and out_score are bit for bit those of oe_ctc_prefix_beam_lm with the same LM arguments; without an LM and with
+ *   length_bonus == 0 the lists and out_ctc are bit for bit those of oe_ctc_prefix_beam.
+ * The graph as the kernel reads it - an Aho-Corasick automaton built by openeat_amd/utils/context_graph.py, which states the
+ * layout once more.  States are trie nodes, the root is 0, n_states <= 2^20:
+ *   ctx_edges (ctx_capacity) slots of 16 bytes {u64 key, i32 next state, i32 0}: the TRIE edges only, in the table format of
+ *     oe_ngram_score (open addressing, linear probing from murmur3_fmix64(key) & (capacity-1), empty key = ~0, capacity a
+ *     power of two, ctx_max_probe the longest displacement), key = state << 32 | token.  A missing edge follows ctx_fail and
+ *     tries again - depth falls with every step, so at most 32 steps and 33 probes; from the root a missing edge stays there.
+ *   ctx_fail (n_states) i32: the longest proper suffix of the state that is a trie node.
+ *   ctx_out (n_states, 2) 32-bit words = (f32 score, i32 link): the score of the phrase that ends exactly at the state (0.0
+ *     if none does) and the nearest state on its fail chain at which a phrase ends (0: none).  The phrases that end at a
+ *     position are kept as this LIST, longest first, and added one by one - a pre-summed value would not reproduce the
+ *     float64 sum above.
+ *   ctx_pend (n_states) i32: the depth of the first state on the chain s, fail[s], .. that has children, which is k(p).
+ * Arguments: those of oe_ctc_prefix_beam_lm, the graph, final, out_bias (B, beam) f64 = bias as it entered out_score, -inf
+ * for a missing slot.  unigrams == NULL means no LM: table, tok2word and out_lm may then be NULL, lm_weight is ignored and
+ * out_lm is not written.  Checked before any launch and reported through oe_last_error: null pointers, beam 1..16,
+ * non-finite weights or c, c < 0, the model checks of oe_ctc_prefix_beam_lm, n_states 1..2^20, a power-of-two ctx_capacity,
+ * ctx_max_probe.  workspace: oe_ctc_prefix_beam_ctx_workspace_bytes bytes, last word zeroed by the caller, as for
+ * oe_ctc_prefix_beam.  One launch, no atomics other than the status word, no allocation, no host read: capturable. */
+size_t oe_ctc_prefix_beam_ctx_workspace_bytes(int B, int Tmax, int beam);
+int oe_ctc_prefix_beam_ctx(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
+                           int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
+                           int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, double lm_weight,
+                           double length_bonus, int eos, const void* ctx_edges, long ctx_capacity, int ctx_max_probe,
+                           const int* ctx_fail, const void* ctx_out, const int* ctx_pend, int ctx_n_states, float ctx_c,
+                           int final, void* workspace, int* out_prefix, int* out_len, double* out_score, double* out_ctc,
+                           double* out_lm, double* out_bias, void* stream);
+
 /* Batched edit distance on the device, one wavefront per pair: the counts behind the reference's error-rate table
  * (tools/compute-wer.py, Calculator.calculate) and optionally the alignment.  These are the semantics every layer refers to.
  * For a reference r[0..n) and a hypothesis h[0..m) of token ids, costs cor 0, sub 1, del 1, ins 1:

@@ -1,6 +1,6 @@
-// CTC prefix beam search on the device, one wavefront per utterance, plain and with n-gram LM shallow fusion: one kernel
-// source, template <bool LM>, two entry points (oe_ctc_prefix_beam, oe_ctc_prefix_beam_lm; semantics in
-// include/openeat_hip.h).
+// CTC prefix beam search on the device, one wavefront per utterance, plain, with n-gram LM shallow fusion and with hotword
+// biasing: one kernel source, template <bool LM, bool CTX>, three entry points (oe_ctc_prefix_beam, oe_ctc_prefix_beam_lm,
+// oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h).
 // (the reference's openeat/models/asr_model.py:359-396: the per-frame Python dict loop).
 //
 // Same arithmetic and the same ordering as the reference and as the host implementation (beam_host.cpp, which stays as
@@ -49,6 +49,16 @@
 // prefixes redo their probes (one lane each) to write the state of the next frame.
 // Bound: latency.  The fusion adds two rounds of <= order-1 independent 16-byte gathers per frame into a table that does
 // not fit LDS.
+//
+// The biasing (CTX = true) is one more prefix-only summand, total(p) + bias(p), bias(p) = hits(p) + c * k(p), read off an
+// Aho-Corasick automaton over the hotword phrases (openeat_amd/utils/context_graph.py builds it).  Per current prefix, in
+// LDS: the automaton state (int), hits (float64) and k = pend[state] (int).  A new-prefix candidate makes its transition in
+// its own lane, next to the LM probes: the trie edge (state, token) in the edge table (ng_find), on a miss fail[state] and
+// again (<= 33 dependent probes; ONE for a prefix that sits in the root), then the phrases that end in the new state, a
+// chain of <= 32 (score, link) reads that is empty for most states.  State, hits and k travel in registers, so the winners
+// need no second pass.  A "stay" entry and an extension that lands on a prefix already in the beam keep that prefix's
+// three values and probe nothing.  Everything it adds sits under `if constexpr (CTX)`; with LM = false it also brings the
+// end-of-utterance re-sort by total, which the plain search has no use for.
 #include <math.h>
 #include "oe_common.h"
 #include "../../include/openeat_hip.h"
@@ -85,6 +95,21 @@ __device__ __forceinline__ double pb_total(double ctc, double lm, int len, doubl
     const double a = lm_weight * lm;
     const double c = length_bonus * (double)len;
     return (ctc + a) + c;
+}
+
+// total(p) of the biased search: pb_total's sum (without an LM term for LM = false), then + bias, each rounded on its own
+template <bool LM>
+__device__ __forceinline__ double pb_total_ctx(double ctc, double lm, int len, double lm_weight, double length_bonus, double bias) {
+#pragma clang fp contract(off)
+    if constexpr (LM) return pb_total(ctc, lm, len, lm_weight, length_bonus) + bias;
+    const double c = length_bonus * (double)len;
+    return (ctc + c) + bias;
+}
+// hits + (double)c * k, the product rounded before the sum
+__device__ __forceinline__ double pb_bias(double hits, float c, int k) {
+#pragma clang fp contract(off)
+    const double credit = (double)c * (double)k;
+    return hits + credit;
 }
 
 // log10 p(w | the prefix whose state is ent / bo); ent_out / bo_out (or null): the state of prefix + w
@@ -124,10 +149,10 @@ __device__ __forceinline__ double pb_extend(const NgModel& m, const int* ent, co
     return term;
 }
 
-struct PbHyp {          // one entry of next_hyps; score: the pruning key; lm: LM only
+struct PbHyp {          // one entry of next_hyps; score: the pruning key; lm: LM only; hits, cstate, cpend: CTX only
     unsigned long long key;
-    double pb, pnb, lm, score;
-    int len, last, parent, tok, order;
+    double pb, pnb, lm, score, hits;
+    int len, last, parent, tok, order, cstate, cpend;
 };
 
 struct PbLmArgs {       // what the fusion takes on top of the plain search (all zero for LM = false)
@@ -138,9 +163,45 @@ struct PbLmArgs {       // what the fusion takes on top of the plain search (all
     double* __restrict__ out_lm;
 };
 
-template <bool LM>
+struct PbCtxArgs : PbLmArgs {       // what the biased search takes on top of that: the context graph (openeat_hip.h)
+    const uint4* __restrict__ edges;
+    unsigned long long edge_mask;   // capacity - 1
+    const int* __restrict__ fail;
+    const int2* __restrict__ out;   // (score bits, link)
+    const int* __restrict__ pend;
+    int edge_max_probe, n_states, final;
+    float c;
+    double* __restrict__ out_bias;
+};
+template <bool CTX> struct PbArgsOf { typedef PbLmArgs type; };          // the two searches without a graph keep their arguments
+template <> struct PbArgsOf<true> { typedef PbCtxArgs type; };
+
+// The automaton's step for a prefix that sits in `state` and takes token `tok`: the new state; hits grows by the scores of
+// the phrases that end there, longest first.  Every index read from a table is checked against n_states.
+__device__ __forceinline__ int pb_ctx_step(const PbCtxArgs& g, int state, int tok, double& hits) {
+    int ns = 0;
+    for (int d = 0; d <= 32; ++d) {                                // depth falls with every fail link: <= 32 of them, 33 probes
+        float nxt, unused;
+        const unsigned long long key = ((unsigned long long)(unsigned)state << 32) | (unsigned)tok;
+        if (ng_find(g.edges, g.edge_mask, g.edge_max_probe, key, nxt, unused) >= 0) { ns = __float_as_int(nxt); break; }
+        if (state == 0) break;
+        state = g.fail[state];
+        if ((unsigned)state >= (unsigned)g.n_states) break;
+    }
+    if ((unsigned)ns >= (unsigned)g.n_states) ns = 0;
+    int t = ns;
+    for (int d = 0; d < 32 && t > 0 && t < g.n_states; ++d) {
+        const int2 o = g.out[t];
+        hits = hits + (double)__int_as_float(o.x);
+        t = o.y;
+    }
+    return ns;
+}
+
+template <bool LM, bool CTX>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ topk_logp, const long long* __restrict__ topk_idx,
-                                                             int Tmax, const int* __restrict__ lens, int beam, int max_len, PbLmArgs la,
+                                                             int Tmax, const int* __restrict__ lens, int beam, int max_len,
+                                                             typename PbArgsOf<CTX>::type la,
                                                              int* __restrict__ hist, int* __restrict__ out_prefix,
                                                              int* __restrict__ out_len, double* __restrict__ out_score,
                                                              int* __restrict__ status) {
@@ -159,6 +220,9 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
     __shared__ int cur_ent[PB_MAXBEAM][PB_H], nx_ent[PB_MAXBEAM][PB_H];
     __shared__ float cur_bo[PB_MAXBEAM][PB_H], nx_bo[PB_MAXBEAM][PB_H];
     __shared__ int tk_w[PB_MAXBEAM], nx_parent[PB_MAXBEAM], nx_tok[PB_MAXBEAM];
+    // CTX only (fin_total: LM or CTX)
+    __shared__ double cur_hits[PB_MAXBEAM], nx_hits[PB_MAXBEAM];
+    __shared__ int cur_cstate[PB_MAXBEAM], cur_cpend[PB_MAXBEAM], nx_cstate[PB_MAXBEAM], nx_cpend[PB_MAXBEAM];
 
     const int b = blockIdx.x, lane = threadIdx.x;
     const int T = min(lens ? lens[b] : Tmax, Tmax);
@@ -172,6 +236,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
 #pragma unroll
             for (int j = 1; j < PB_H; ++j) { cur_ent[0][j] = -1; cur_bo[0][j] = 0.f; }
         }
+        if constexpr (CTX) { cur_hits[0] = 0.0; cur_cstate[0] = 0; cur_cpend[0] = 0; }            // the empty prefix: the root, k = 0
     }
     __syncthreads();
     int* hist_b = hist + (long)b * Tmax * beam * 2;
@@ -217,6 +282,11 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                         cand[c].pnb = rep ? a : pb_log_add3(NEG, a, bb);
                         cand[c].order = 2 * p + 1;
                         if constexpr (LM) cand[c].lm = cur_lm[h] + pb_extend(la.m, cur_ent[h], cur_bo[h], tk_w[j], nullptr, nullptr);
+                        if constexpr (CTX) {
+                            double hits = cur_hits[h];
+                            const int ns = pb_ctx_step(la, cur_cstate[h], s, hits);
+                            cand[c].hits = hits; cand[c].cstate = ns; cand[c].cpend = la.pend[ns];
+                        }
                     }
                 }
             }
@@ -253,13 +323,17 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                 PbHyp& e = cand[PB_MAXC];
                 e.key = cur_key[n]; e.len = cur_len[n]; e.last = last; e.parent = n; e.tok = -1; e.pb = npb; e.pnb = npnb; e.order = order;
                 if constexpr (LM) e.lm = cur_lm[n];
+                if constexpr (CTX) { e.hits = cur_hits[n]; e.cstate = cur_cstate[n]; e.cpend = cur_cpend[n]; }
             }
         }
 #pragma unroll
         for (int c = 0; c <= PB_MAXC; ++c)
             if (alive[c]) {
                 cand[c].score = pb_log_add2(cand[c].pb, cand[c].pnb);
-                if constexpr (LM) cand[c].score = pb_total(cand[c].score, cand[c].lm, cand[c].len, la.lm_weight, la.length_bonus);
+                if constexpr (CTX)
+                    cand[c].score = pb_total_ctx<LM>(cand[c].score, cand[c].lm, cand[c].len, la.lm_weight, la.length_bonus,
+                                                     pb_bias(cand[c].hits, la.c, cand[c].cpend));
+                else if constexpr (LM) cand[c].score = pb_total(cand[c].score, cand[c].lm, cand[c].len, la.lm_weight, la.length_bonus);
             }
 
         // ---- the best `beam` entries by (score descending, first touch ascending)
@@ -285,6 +359,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
                     if (c == bc) {
                         nx_key[r] = cand[c].key; nx_pb[r] = cand[c].pb; nx_pnb[r] = cand[c].pnb; nx_len[r] = cand[c].len; nx_last[r] = cand[c].last;
                         if constexpr (LM) { nx_lm[r] = cand[c].lm; nx_parent[r] = cand[c].parent; nx_tok[r] = cand[c].tok; }
+                        if constexpr (CTX) { nx_hits[r] = cand[c].hits; nx_cstate[r] = cand[c].cstate; nx_cpend[r] = cand[c].cpend; }
                         hist_b[((long)t * beam + r) * 2] = cand[c].parent;
                         hist_b[((long)t * beam + r) * 2 + 1] = cand[c].tok;
                         alive[c] = false;
@@ -314,19 +389,28 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
 #pragma unroll
                 for (int j = 0; j < PB_H; ++j) { cur_ent[lane][j] = nx_ent[lane][j]; cur_bo[lane][j] = nx_bo[lane][j]; }
             }
+            if constexpr (CTX) { cur_hits[lane] = nx_hits[lane]; cur_cstate[lane] = nx_cstate[lane]; cur_cpend[lane] = nx_cpend[lane]; }
         }
         ncur = nsel;
         __syncthreads();
     }
 
-    // ---- LM, end of the utterance: the </s> term, then the survivors stably re-sorted by total
-    double lm = 0.0, ctc = NEG, total = NEG;
-    if constexpr (LM) {
+    // ---- LM / CTX, end of the utterance: the </s> term, the pending credit dropped if final, then the survivors stably
+    // re-sorted by total
+    double lm = 0.0, ctc = NEG, total = NEG, bias = 0.0;
+    if constexpr (LM || CTX) {
         if (lane < ncur) {
-            lm = cur_lm[lane];
-            if (la.eos) lm = lm + pb_extend(la.m, cur_ent[lane], cur_bo[lane], la.m.eos_word, nullptr, nullptr);
+            if constexpr (LM) {
+                lm = cur_lm[lane];
+                if (la.eos) lm = lm + pb_extend(la.m, cur_ent[lane], cur_bo[lane], la.m.eos_word, nullptr, nullptr);
+            }
             ctc = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
-            total = pb_total(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus);
+            if constexpr (CTX) {
+                bias = la.final ? cur_hits[lane] : pb_bias(cur_hits[lane], la.c, cur_cpend[lane]);
+                total = pb_total_ctx<LM>(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus, bias);
+            } else {
+                total = pb_total(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus);
+            }
             fin_total[lane] = total;
         }
         __syncthreads();
@@ -336,7 +420,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
     if (lane < beam) {
         if (lane < ncur) {
             int rank = lane;
-            if constexpr (LM) {
+            if constexpr (LM || CTX) {
                 rank = 0;
                 for (int i = 0; i < ncur; ++i) {
                     const double ti = fin_total[i];
@@ -345,7 +429,12 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             }
             const long o = (long)b * beam + rank;
             const int len = cur_len[lane];
-            if constexpr (LM) {
+            if constexpr (CTX) {
+                out_score[o] = total;
+                la.out_ctc[o] = ctc;
+                if constexpr (LM) la.out_lm[o] = lm;
+                la.out_bias[o] = bias;
+            } else if constexpr (LM) {
                 out_score[o] = total;
                 la.out_ctc[o] = ctc;
                 la.out_lm[o] = lm;
@@ -364,6 +453,10 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             const long o = (long)b * beam + lane;
             out_score[o] = NEG;
             if constexpr (LM) { la.out_ctc[o] = NEG; la.out_lm[o] = NEG; }
+            if constexpr (CTX) {
+                if constexpr (!LM) la.out_ctc[o] = NEG;
+                la.out_bias[o] = NEG;
+            }
             out_len[o] = -1;
         }
     }
@@ -374,6 +467,7 @@ static size_t pb_hist_words(int B, int Tmax, int beam) { return (size_t)B * (siz
 
 extern "C" size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
 extern "C" size_t oe_ctc_prefix_beam_lm_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
+extern "C" size_t oe_ctc_prefix_beam_ctx_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
 
 // fn: the entry point, for its messages
 static int pb_check_shape(const char* fn, int B, int Tmax, int max_len, int beam) {
@@ -382,12 +476,13 @@ static int pb_check_shape(const char* fn, int B, int Tmax, int max_len, int beam
     return 0;
 }
 
-template <bool LM>
+template <bool LM, bool CTX>
 static int pb_launch(const char* name, const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                     int max_len, const PbLmArgs& la, void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream) {
+                     int max_len, const typename PbArgsOf<CTX>::type& la, void* workspace, int* out_prefix, int* out_len,
+                     double* out_score, void* stream) {
     int* hist = (int*)workspace;
     int* status = hist + pb_hist_words(B, Tmax, beam);            // the caller zeroes this word and reads it back
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel<LM>, dim3(B), dim3(64), 0, (hipStream_t)stream, topk_logp, topk_idx, Tmax, lens, beam,
+    hipLaunchKernelGGL((ctc_prefix_beam_kernel<LM, CTX>), dim3(B), dim3(64), 0, (hipStream_t)stream, topk_logp, topk_idx, Tmax, lens, beam,
                        max_len, la, hist, out_prefix, out_len, out_score, status);
     OE_LAUNCH_CHECK(name);
     return 0;
@@ -397,8 +492,8 @@ extern "C" int oe_ctc_prefix_beam(const float* topk_logp, const long long* topk_
                                   int max_len, void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream) {
     OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score, "oe_ctc_prefix_beam: null pointer");
     if (pb_check_shape("oe_ctc_prefix_beam", B, Tmax, max_len, beam)) return -1;
-    return pb_launch<false>("ctc_prefix_beam", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, PbLmArgs{}, workspace, out_prefix,
-                            out_len, out_score, stream);
+    return pb_launch<false, false>("ctc_prefix_beam", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, PbLmArgs{}, workspace, out_prefix,
+                                   out_len, out_score, stream);
 }
 
 extern "C" int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
@@ -415,6 +510,42 @@ extern "C" int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* to
     OE_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", fn, V);
     OE_REQUIRE(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight and length_bonus must be finite", fn);
     la.lm_weight = lm_weight; la.length_bonus = length_bonus; la.eos = eos; la.out_ctc = out_ctc; la.out_lm = out_lm;
-    return pb_launch<true>("ctc_prefix_beam_lm", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix, out_len,
-                           out_score, stream);
+    return pb_launch<true, false>("ctc_prefix_beam_lm", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix, out_len,
+                                  out_score, stream);
+}
+
+extern "C" int oe_ctc_prefix_beam_ctx(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
+                                      int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
+                                      int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V,
+                                      double lm_weight, double length_bonus, int eos, const void* ctx_edges, long ctx_capacity,
+                                      int ctx_max_probe, const int* ctx_fail, const void* ctx_out, const int* ctx_pend,
+                                      int ctx_n_states, float ctx_c, int final, void* workspace, int* out_prefix, int* out_len,
+                                      double* out_score, double* out_ctc, double* out_lm, double* out_bias, void* stream) {
+    const char* fn = "oe_ctc_prefix_beam_ctx";
+    OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score && out_ctc && out_bias, "%s: null pointer", fn);
+    OE_REQUIRE(ctx_edges && ctx_fail && ctx_out && ctx_pend, "%s: null pointer (context graph)", fn);
+    if (pb_check_shape(fn, B, Tmax, max_len, beam)) return -1;
+    PbCtxArgs la{};
+    if (unigrams) {
+        OE_REQUIRE(table && tok2word && out_lm, "%s: null pointer (model)", fn);
+        if (ng_model_args(fn, unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &la.m)) return -1;
+        OE_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", fn, V);
+        OE_REQUIRE(isfinite(lm_weight), "%s: lm_weight must be finite", fn);
+        la.lm_weight = lm_weight; la.eos = eos; la.out_lm = out_lm;
+    }
+    OE_REQUIRE(isfinite(length_bonus), "%s: length_bonus must be finite", fn);
+    OE_REQUIRE(ctx_n_states >= 1 && ctx_n_states <= (1 << 20), "%s: n_states must be 1..2^20 (got %d)", fn, ctx_n_states);
+    OE_REQUIRE(ctx_capacity >= 2 && (ctx_capacity & (ctx_capacity - 1)) == 0, "%s: the graph's capacity must be a power of two >= 2 (got %ld)",
+               fn, ctx_capacity);
+    OE_REQUIRE(ctx_max_probe >= 0 && ctx_max_probe < ctx_capacity, "%s: bad max_probe %d of the graph", fn, ctx_max_probe);
+    OE_REQUIRE(isfinite(ctx_c) && ctx_c >= 0.f, "%s: the partial credit c must be finite and >= 0", fn);
+    la.length_bonus = length_bonus; la.out_ctc = out_ctc;
+    la.edges = (const uint4*)ctx_edges; la.edge_mask = (unsigned long long)(ctx_capacity - 1); la.edge_max_probe = ctx_max_probe;
+    la.fail = ctx_fail; la.out = (const int2*)ctx_out; la.pend = ctx_pend; la.n_states = ctx_n_states; la.c = ctx_c;
+    la.final = final; la.out_bias = out_bias;
+    if (unigrams)
+        return pb_launch<true, true>("ctc_prefix_beam_ctx", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix,
+                                     out_len, out_score, stream);
+    return pb_launch<false, true>("ctc_prefix_beam_ctx", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix,
+                                  out_len, out_score, stream);
 }

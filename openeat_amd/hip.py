@@ -270,6 +270,9 @@ _SIGNATURES = {
     "oe_ngram_score": (I, [P, I, P, L, I, I, I, I, I, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_ctc_prefix_beam_lm_workspace_bytes": (SZ, [I, I, I]),
     "oe_ctc_prefix_beam_lm": (I, [P, P, I, I, P, I, I, P, I, P, L, I, I, I, I, I, P, I, D, D, I, P, P, P, P, P, P, P]),
+    "oe_ctc_prefix_beam_ctx_workspace_bytes": (SZ, [I, I, I]),
+    "oe_ctc_prefix_beam_ctx": (I, [P, P, I, I, P, I, I, P, I, P, L, I, I, I, I, I, P, I, D, D, I, P, L, I, P, P, P, I, F, I, P, P, P, P, P,
+                               P, P, P]),
     "oe_edit_distance_workspace_bytes": (SZ, [I, I, I]),
     "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_grad_norm_workspace_floats": (SZ, []),
@@ -584,6 +587,34 @@ def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, len
         return prefixes, plen, total, ctc, lms, ws[-1:]
     check_prefix_beam_status(ws[-1], "oe_ctc_prefix_beam_lm")
     return _nbest_lists(prefixes, plen, total, ctc, lms)
+
+
+def ctc_prefix_beam_ctx_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, graph, lm=None,
+                               lm_weight: float = 0.0, length_bonus: float = 0.0, eos: bool = True, final: bool = True,
+                               raw: bool = False):
+    """CTC prefix beam search with hotword biasing (oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h): the inputs of
+    ctc_prefix_beam_device plus `graph`, an openeat_amd.utils.context_graph.ContextGraph, and optionally `lm`, an NgramLM,
+    fused as in ctc_prefix_beam_lm_device -> per utterance [(prefix tuple, total, ctc, lm, bias)] sorted by total, lm = 0.0
+    when no LM is given.  final: the pending partial credit is dropped at the end of the utterance.  raw=True: no copy at
+    all - the device tensors (prefixes, lengths, total / ctc / lm / bias (B, beam) float64, -inf where missing; lm all zero
+    without an LM) and the status word tensor the caller checks after its own synchronisation."""
+    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (total, ctc, lms, bias) = _prefix_beam_buffers("ctc_prefix_beam_ctx", top_logp, top_idx,
+                                                                                                   beam, 4)
+    edges, fail, out, pend = graph.device_tables(top_logp.device)
+    if lm is None:
+        lms.zero_()
+        model = (None, 0, None, 0, 0, 0, 0, 0, 0, None, 0)
+    else:
+        uni, table, tok2word = lm.device_tables(top_logp.device)
+        model = (uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word, tok2word,
+                 int(tok2word.shape[0]))
+    call("oe_ctc_prefix_beam_ctx", top_logp, top_idx, B, T, lens, beam, ml, *model, float(lm_weight), float(length_bonus), int(bool(eos)),
+         edges, graph.capacity, graph.max_probe, fail, out, pend, graph.n_states, float(graph.context_score), int(bool(final)), ws,
+         prefixes, plen, total, ctc, None if lm is None else lms, bias)
+    if raw:
+        return prefixes, plen, total, ctc, lms, bias, ws[-1:]
+    check_prefix_beam_status(ws[-1], "oe_ctc_prefix_beam_ctx")
+    return _nbest_lists(prefixes, plen, total, ctc, lms, bias)
 
 
 def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, lens, beam: int, n_threads: int = 0):

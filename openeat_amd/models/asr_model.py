@@ -43,6 +43,17 @@ def _require_fused_beam(lm, beam_size):
         raise ValueError(f"the LM-fused CTC beam search supports beam sizes 1..16 (got {beam_size})")
 
 
+def _require_context_beam(context, beam_size):
+    """The hotword-biased prefix search exists on the device only (beam.hip): a ContextGraph, the device beam, beam <= 16."""
+    from openeat_amd.utils.context_graph import ContextGraph
+    if not isinstance(context, ContextGraph):
+        raise ValueError(f"the hotword-biased CTC beam search needs a ContextGraph (got {type(context).__name__})")
+    if not DEVICE_BEAM:
+        raise ValueError("the hotword-biased CTC beam search runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
+    if not 1 <= beam_size <= 16:
+        raise ValueError(f"the hotword-biased CTC beam search supports beam sizes 1..16 (got {beam_size})")
+
+
 def _graph_call(cache, key, fn, args):
     """fn(*args) through a per-key HIP graph: first call eager (lazy state must exist before a capture) and captured for
     the next time, later calls copy the arguments into the capture's static inputs and replay.  Outputs are the capture's
@@ -361,6 +372,24 @@ class ASRModel(torch.nn.Module):
         top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
         return hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, lm, lm_weight, length_bonus, eos)
 
+    @torch.no_grad()
+    def ctc_context_beam_search(self, features, features_length, beam_size: int, context, lm=None, lm_weight: float = 0.0,
+                                length_bonus: float = 0.0, eos: bool = True):
+        """CTC prefix beam search with hotword biasing, batched (oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h):
+        prefixes are pruned every frame by ctc_lm_beam_search's total (the LM term only with an NgramLM) + bias(prefix), the
+        score `context`, a ContextGraph, gives the hotwords a prefix holds, plus a per-token credit while one is half spoken;
+        at the end of the utterance the pending credit is dropped.  -> per utterance [(prefix tuple, total, ctc, lm, bias)]
+        sorted by total.  Needs the device beam and beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
+        from openeat_amd import hip
+        _require_context_beam(context, beam_size)
+        if lm is not None:
+            _require_fused_beam(lm, beam_size)
+        assert features.shape[0] == features_length.shape[0]
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1)
+        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
+        return hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens.to(torch.int32), beam_size, context, lm, lm_weight, length_bonus, eos)
+
     def attention_rescoring(self, features, features_length, beam_size: int, ctc_weight: float = 0.0,
                             reverse_weight: float = 0.0, lm: Optional[torch.nn.Module] = None, lm_weight: float = 0,
                             autoregressive: bool = True, token2char: dict = {}):
@@ -418,7 +447,8 @@ class ASRModel(torch.nn.Module):
                                   ctc_weight: float = 0.0, reverse_weight: float = 0.0,
                                   lm: Optional[torch.nn.Module] = None, lm_weight: float = 0.0,
                                   use_graphs: Optional[bool] = None, first_pass_lm: bool = False,
-                                  first_pass_lm_weight: Optional[float] = None, length_bonus: float = 0.0) -> List[List[int]]:
+                                  first_pass_lm_weight: Optional[float] = None, length_bonus: float = 0.0,
+                                  context=None) -> List[List[int]]:
         """Batched form of attention_rescoring (the reference handles one utterance per call,
         asr_model.py:444): ONE encoder pass and ONE fused log-softmax top-k for the whole batch, the prefix
         recursion of every utterance on its own valid frames (one wave each on the device; OE_DEVICE_BEAM=0: native host
@@ -426,7 +456,10 @@ class ASRModel(torch.nn.Module):
         use_graphs (default: OE_DECODE_GRAPHS, off): replay the two stages from HIP graphs cached per shape.
         first_pass_lm: with an NgramLM and lm_weight > 0 the n-best lists come from the LM-fused search (ctc_lm_beam_search's
         kernel, pruning by CTC + first_pass_lm_weight * LM + length_bonus * length; the weight defaults to lm_weight); the
-        rescoring itself is unchanged and takes the prefixes' plain CTC scores."""
+        rescoring itself is unchanged and takes the prefixes' plain CTC scores.
+        context: a ContextGraph of hotwords - the n-best lists come from the biased search (ctc_context_beam_search's kernel,
+        with the LM only under the first_pass_lm rule, and with length_bonus), and every hypothesis' final bias is added to
+        its mixed score, since nothing else in the rescoring knows about hotwords.  Device beam only."""
         from openeat_amd import hip
         device = features.device
         B = features.shape[0]
@@ -439,14 +472,19 @@ class ASRModel(torch.nn.Module):
         if first_pass_lm and isinstance(lm, NgramLM) and lm_weight > 0:
             _require_fused_beam(lm, beam_size)
             fuse = (lm, float(lm_weight if first_pass_lm_weight is None else first_pass_lm_weight), float(length_bonus))
+        if context is not None:
+            _require_context_beam(context, beam_size)
+            if fuse is None:                                       # no LM in the first pass: the length bonus alone
+                fuse = (None, 0.0, float(length_bonus))
+            fuse = fuse + (context,)
         if on_device and graphs:
             return self._rescoring_batch_graphs(features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight, fuse)
         if on_device:
-            encoder_out, encoder_mask, pre, plen, ctc_scores, bad = self._rescore_stage1(features, features_length, beam_size, fuse)
+            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, *bias = self._rescore_stage1(features, features_length, beam_size, fuse)
             Lm = max(int(plen.max()), 1)                           # the one host sync of the n-best stage
             hip.check_prefix_beam_status(bad)
             toks, n, mean_len = self._rescore_stage2(encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight,
-                                                     reverse_weight, lm, lm_weight)
+                                                     reverse_weight, lm, lm_weight, *bias)
             self.last_nbest_mean_len = float(mean_len)
             toks, n = toks.cpu(), n.cpu().tolist()
             return [toks[b, : n[b]].tolist() for b in range(B)]
@@ -474,11 +512,18 @@ class ASRModel(torch.nn.Module):
     def _rescore_stage1(self, features, features_length, beam_size, fuse=None):
         """Encoder, CTC projection, fused log-softmax top-k, prefix recursion - all on the device, no host sync.
         Returns encoder_out, encoder_mask, prefixes (R, T') int32, lengths (R) int32 (-1: the slot does not exist), CTC
-        scores (R) float64, status word.  fuse = (NgramLM, weight, length bonus): the LM-fused recursion picks the prefixes."""
+        scores (R) float64, status word.  fuse = (NgramLM, weight, length bonus): the LM-fused recursion picks the prefixes;
+        fuse = (NgramLM or None, weight, length bonus, ContextGraph): the hotword-biased one does, and the hypotheses' final
+        bias (R) float64 is returned as a seventh value."""
         from openeat_amd import hip
         encoder_out, encoder_mask, _ = self._encode(features, features_length)
         lens = encoder_mask.squeeze(1).sum(1)
         top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
+        if fuse is not None and len(fuse) == 4:
+            pre, plen, _, ctc_scores, _, bias, bad = hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens.to(torch.int32), beam_size, fuse[3],
+                                                                                   fuse[0], fuse[1], fuse[2], eos=True, final=True, raw=True)
+            R = pre.shape[0] * beam_size
+            return encoder_out, encoder_mask, pre.view(R, -1), plen.view(R), ctc_scores.view(R), bad, bias.view(R)
         if fuse is not None:
             pre, plen, _, ctc_scores, _, bad = hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, fuse[0],
                                                                              fuse[1], fuse[2], eos=True, raw=True)
@@ -487,9 +532,10 @@ class ASRModel(torch.nn.Module):
         R = pre.shape[0] * beam_size
         return encoder_out, encoder_mask, pre.view(R, -1), plen.view(R), ctc_scores.view(R), bad
 
-    def _rescore_stage2(self, encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight, reverse_weight, lm, lm_weight):
+    def _rescore_stage2(self, encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight, reverse_weight, lm, lm_weight,
+                        bias=None):
         """The n-best lists as device tensors -> (tokens (B, Lm) of the rescored pick, their lengths (B), mean n-best length).
-        Lm >= the longest hypothesis (any padding is ignore_id and masked)."""
+        Lm >= the longest hypothesis (any padding is ignore_id and masked).  bias (R) float64: added to the mixed scores."""
         device = pre.device
         B = encoder_out.shape[0]
         missing = plen < 0
@@ -498,13 +544,14 @@ class ASRModel(torch.nn.Module):
         ori = ori.masked_fill(torch.arange(Lm, device=device).unsqueeze(0) >= hl.unsqueeze(1), self.ignore_id)
         ctc_scores = ctc_scores.masked_fill(missing, -float("inf"))
         best = self._rescore_scores(encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight,
-                                    lm, lm_weight)
+                                    lm, lm_weight, bias)
         pick = best + torch.arange(B, device=device) * beam_size
         return ori.index_select(0, pick), hl.index_select(0, pick), hl.float().mean()
 
     def _rescore_scores(self, encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight, lm,
-                        lm_weight):
-        """asr_model.py:504-528 for all B x beam hypotheses at once: index of the best hypothesis per utterance."""
+                        lm_weight, bias=None):
+        """asr_model.py:504-528 for all B x beam hypotheses at once: index of the best hypothesis per utterance.
+        bias (R) float64 or None: the hypotheses' hotword scores, added to the mix."""
         device = ori.device
         B = encoder_out.shape[0]
         R = B * beam_size
@@ -538,6 +585,8 @@ class ASRModel(torch.nn.Module):
             lm_tok = ops.logprob_gather(lm.logits(hyps_pad, hl + 1), tok) if hasattr(lm, "logits") else \
                 lm.log_probs(hyps_pad, hl + 1).gather(2, tok.unsqueeze(2)).squeeze(2)
             score = score + (lm_tok * valid).sum(1).double() * lm_weight
+        if bias is not None:
+            score = score + bias
         score = score.masked_fill(missing, -float("inf"))         # (0 * -inf above would be nan: the slot is out whatever the weights)
         return score.view(B, beam_size).argmax(1)
 
@@ -556,15 +605,20 @@ class ASRModel(torch.nn.Module):
             k1 = ("s1", tuple(features.shape), beam_size)
             if fuse is not None:                                   # the fused recursion reads this model's tables and these weights
                 k1 = k1 + (id(fuse[0]), fuse[1], fuse[2], True)
+                if len(fuse) == 4:                                 # and the biased one this graph's: the object itself (it hashes by
+                    k1 = k1 + (fuse[3],)                           # identity), so the tables a capture points at live as long as it
             out1 = _graph_call(cache, k1, lambda f, fl: self._rescore_stage1(f, fl, beam_size, fuse), (features, features_length))
-            encoder_out, encoder_mask, pre, plen, ctc_scores, bad = out1
+            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, *bias = out1
             Lm = max(int(plen.max()), 1)
             hip.check_prefix_beam_status(bad)
             Lb = min(-(-Lm // 16) * 16, pre.shape[1])
             k2 = ("s2", tuple(encoder_out.shape), beam_size, Lb, float(ctc_weight), float(reverse_weight), id(lm), float(lm_weight))
+            if bias:                                               # one more input: a graph of its own
+                k2 = k2 + ("bias",)
             toks, n, mean_len = _graph_call(
-                cache, k2, lambda eo, em, p, pl, cs: self._rescore_stage2(eo, em, p, pl, cs, Lb, beam_size, ctc_weight, reverse_weight,
-                                                                         lm, lm_weight), (encoder_out, encoder_mask, pre, plen, ctc_scores))
+                cache, k2, lambda eo, em, p, pl, cs, *bi: self._rescore_stage2(eo, em, p, pl, cs, Lb, beam_size, ctc_weight, reverse_weight,
+                                                                              lm, lm_weight, *bi),
+                (encoder_out, encoder_mask, pre, plen, ctc_scores, *bias))
         finally:
             common.STATIC_SHAPES = static_before
         self.last_nbest_mean_len = float(mean_len)
