@@ -818,6 +818,48 @@ int oe_edit_distance(const int* ref, long ref_ld, const int* ref_lens, int group
                      const int* hyp_lens, int P, int Nmax, int Mmax, int* counts, int* ref_to_hyp, void* workspace,
                      void* stream);
 
+/* CTC prefix scores for the joint CTC/attention one-pass beam search (Watanabe et al. 2017, Hori et al. 2017): the attention
+ * decoder proposes tokens and the CTC prefix score of every proposal enters the pruning key.  These are the semantics every
+ * layer refers to (ops.ctc_prefix_score, utils/joint_search.py, ASRModel.ctc_attention_beam_search; the yardstick is
+ * tests/ctc_prefix_score_ref.py).
+ *
+ * y[t, k] are the CTC log-probabilities of one utterance, t = 0..T-1, T its valid frame count; column `blank` is the blank.
+ * A hypothesis is a token sequence g (the tokens after <sos>).  Its state is r[t, 0] (non-blank) and r[t, 1] (blank): the
+ * log-probability of all alignments of frames 0..t that collapse to exactly g and end in a non-blank resp. a blank.
+ *   The empty hypothesis: r[t, 0] = -inf, r[t, 1] = y[0, blank] + .. + y[t, blank], added left to right.
+ *   Extension h = g . c with c neither blank nor <eos>:
+ *     n[0, 0] = y[0, c] if g is empty else -inf;  n[0, 1] = -inf;  psi = n[0, 0]
+ *     for t = 1..T-1:
+ *       phi     = r[t-1, 1]                        if c == the last token of g
+ *                 log_add(r[t-1, 0], r[t-1, 1])    otherwise
+ *       n[t, 0] = log_add(n[t-1, 0], phi) + y[t, c]
+ *       n[t, 1] = log_add(n[t-1, 0], n[t-1, 1]) + y[t, blank]
+ *       psi     = log_add(psi, phi + y[t, c])
+ *   psi(h) is the log-probability that the utterance's label sequence starts with h; n is h's state.
+ *   c blank or outside 0..V-1: psi = -inf (this is tested first).  c == <eos>: psi = log_add(r[T-1, 0], r[T-1, 1]), the full
+ *   CTC likelihood of g.  T == 0: <eos> after the empty hypothesis scores 0, everything else -inf.  In none of these cases
+ *   is a state produced: the candidate's cand_state entries are not written.
+ *   log_add(a, b) = max + log(exp(a - max) + exp(b - max)); with both arguments -inf it is -inf, never NaN.  All arithmetic
+ *   is float64, as in the prefix-beam kernels.
+ *
+ * logp (B, Tmax, ldv) f32 with ldv >= V; lens (B) i32 valid frames (clamped to 0..Tmax by the kernel) or NULL = Tmax.  There
+ * are R = B * group rows; row r belongs to utterance r / group.
+ * oe_ctc_prefix_score_init writes the empty hypothesis' state of every row into state (R, Tmax, 2) f64.
+ * oe_ctc_prefix_score: state_in (R, Tmax, 2) f64 the hypotheses' states; hyp_len (R) i32 their token counts (0: the empty
+ * one), < 0 = the slot does not exist (as out_len of oe_ctc_prefix_beam): all its psi are -inf and its cand_state rows are
+ * untouched; last_tok (R) i32, read where hyp_len > 0; cand (R, C) i32 candidate tokens, 1 <= C <= 64.
+ *   out: psi (R, C) f64;  cand_state (R, Tmax, C, 2) f64 or NULL: the state of hypothesis r extended by its candidate j at
+ *        [r, t, j, :].  psi is bit-identical with and without cand_state.
+ * Frames at or beyond an utterance's length are never read or written, in any buffer.
+ * Null pointers (other than lens and cand_state), C outside 1..64, group < 1, ldv < V and a blank outside 0..V-1 are
+ * reported through oe_last_error before any launch.  One wavefront per row, one lane per candidate; one launch, no workspace,
+ * no atomics, no allocation, no synchronisation, no host-side state: capturable. */
+int oe_ctc_prefix_score_init(const float* logp, const int* lens, int B, int Tmax, int V, long ldv, int group, int blank,
+                             double* state, void* stream);
+int oe_ctc_prefix_score(const float* logp, const int* lens, int B, int Tmax, int V, long ldv, int group, const double* state_in,
+                        const int* hyp_len, const int* last_tok, const int* cand, int C, int blank, int eos, double* psi,
+                        double* cand_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

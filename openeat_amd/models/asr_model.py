@@ -659,3 +659,51 @@ class ASRModel(torch.nn.Module):
         scores = scores.view(B, beam_size)
         best_index = torch.argmax(scores, dim=-1).long() + torch.arange(B, dtype=torch.long, device=device) * beam_size
         return torch.index_select(hyps, 0, best_index)[:, 1:]
+
+    @torch.no_grad()
+    def ctc_attention_beam_search(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int = 10,
+                                  ctc_weight: float = 0.3, length_bonus: float = 0.0, ctc_candidates: Optional[int] = None,
+                                  max_len: Optional[int] = None, nbest: bool = False):
+        """Joint CTC/attention one-pass beam search (not in the reference; semantics in utils/joint_search.py and, for the CTC
+        prefix score, include/openeat_hip.h): the decoder proposes `ctc_candidates` tokens per hypothesis (default
+        min(2 beam_size, V, 64)), and each is ranked by (1 - ctc_weight) * attention + ctc_weight * CTC prefix score +
+        length_bonus * length.  One encoder pass and one log-softmax of the CTC logits for the batch, then per step one
+        decoder.forward_one_step over all B x beam hypotheses and one oe_ctc_prefix_score launch (none with ctc_weight == 0).
+        Unlike recognize, which reproduces the reference's un-reordered decoder cache on purpose, this search reorders the
+        per-layer decoder cache by the surviving parents after every pruning.  max_len: the step limit (default: the batch's
+        encoder length, as in recognize).  -> per utterance the best hypothesis' tokens without <eos>; nbest: per utterance
+        [(tokens, total, att, ctc)], finished hypotheses first, each group by total (ctc is 0 with ctc_weight == 0)."""
+        from openeat_amd.utils.joint_search import joint_beam_search
+        if not 0.0 <= ctc_weight <= 1.0:
+            raise ValueError(f"ctc_weight must lie in [0, 1] (got {ctc_weight})")
+        if self.ctc_weight == 1.0:
+            raise ValueError("this model was built with ctc_weight == 1.0: its decoder was never trained")
+        C = min(2 * beam_size, self.vocab_size, 64) if ctc_candidates is None else int(ctc_candidates)
+        if not 1 <= C <= min(64, self.vocab_size):
+            raise ValueError(f"ctc_candidates must lie in 1..{min(64, self.vocab_size)} (got {C})")
+        if beam_size < 1:
+            raise ValueError(f"beam_size must be >= 1 (got {beam_size})")
+        assert features.shape[0] == features_length.shape[0]
+        device = features.device
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1).to(torch.int32)
+        logp = ops.log_softmax_rows(self.ctc.logits(encoder_out))
+        R = features.shape[0] * beam_size
+        memory = encoder_out.repeat_interleave(beam_size, dim=0)
+        memory_mask = encoder_mask.repeat_interleave(beam_size, dim=0)
+        sos = torch.full((R, 1), self.sos, dtype=torch.long, device=device)
+        cache = None
+
+        def step_fn(tokens, parents):
+            nonlocal cache
+            hyps = torch.cat((sos, tokens), dim=1)
+            if parents is not None:                                # the survivors' own histories, not their slots'
+                cache = [c.index_select(0, parents) for c in cache]
+            hyps_mask = subsequent_mask(hyps.size(1), device=device).unsqueeze(0).repeat(R, 1, 1)
+            p, cache, _ = self.decoder.forward_one_step(hyps, hyps_mask, memory, memory_mask, cache=cache)
+            return ops.log_softmax_rows(p)
+
+        res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len)
+        if nbest:
+            return [[(t, total, att, ctc) for t, total, att, ctc, _ in nb] for nb in res]
+        return [nb[0][0] if nb else [] for nb in res]

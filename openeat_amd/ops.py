@@ -2421,6 +2421,66 @@ def edit_distance(ref, ref_lens, hyp, hyp_lens, group: int = 1, align: bool = Fa
     return (counts, r2h) if align else counts
 
 
+def _prefix_score_logp(name, logp, lens, group):
+    if not (isinstance(logp, torch.Tensor) and logp.is_cuda) or not (lens is None or (isinstance(lens, torch.Tensor) and lens.is_cuda)):
+        raise TypeError(f"{name}: openeat_amd ops need CUDA tensors; there is no CPU fallback")
+    if logp.dtype != torch.float32 or logp.dim() != 3:
+        raise TypeError(f"{name}: logp must be a float32 (B, Tmax, V) tensor (got {logp.dtype}, {tuple(logp.shape)})")
+    if lens is not None and (lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != logp.shape[:1]):
+        raise TypeError(f"{name}: lens (B) must be an integer tensor")
+    group = int(group)
+    if group < 1:
+        raise ValueError(f"{name}: group must be >= 1 (got {group})")
+    return logp.contiguous(), (None if lens is None else lens.to(torch.int32).contiguous()), group
+
+
+def ctc_prefix_score_init(logp, lens, group: int = 1, blank: int = 0):
+    """The empty hypothesis' CTC prefix state for R = B * group rows (oe_ctc_prefix_score_init; semantics in
+    include/openeat_hip.h): logp (B, Tmax, V) float32 CTC log-probabilities, lens (B) valid frames or None, on the device.
+    -> state (R, Tmax, 2) float64; what lies at or behind an utterance's length is left as allocated.  Capturable."""
+    logp, len32, group = _prefix_score_logp("ctc_prefix_score_init", logp, lens, group)
+    B, Tmax, V = (int(s) for s in logp.shape)
+    state = torch.empty(B * group, Tmax, 2, dtype=torch.float64, device=logp.device)
+    hip.call("oe_ctc_prefix_score_init", logp, len32, B, Tmax, V, V, group, int(blank), state)
+    return state
+
+
+def ctc_prefix_score(logp, lens, state_in, hyp_len, last_tok, cand, eos: int, group: int = 1, blank: int = 0, states: bool = True,
+                     cand_state=None):
+    """CTC prefix scores of C candidate extensions of each of R = B * group hypotheses (oe_ctc_prefix_score; semantics in
+    include/openeat_hip.h): logp (B, Tmax, V) float32, lens (B) or None, state_in (R, Tmax, 2) float64, hyp_len (R) token
+    counts (< 0: the slot does not exist, its psi are -inf), last_tok (R), cand (R, C) with 1 <= C <= 64, all on the device.
+    -> psi (R, C) float64 and, with `states`, cand_state (R, Tmax, C, 2) float64 - written into the tensor given as
+    `cand_state` when there is one; entries of candidates that produce no state (blank, out of range, <eos>), of missing
+    slots and of frames behind an utterance's length are not written.  No host read: capturable."""
+    name = "ctc_prefix_score"
+    logp, len32, group = _prefix_score_logp(name, logp, lens, group)
+    ts = (state_in, hyp_len, last_tok, cand)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError(f"{name}: openeat_amd ops need CUDA tensors; there is no CPU fallback")
+    B, Tmax, V = (int(s) for s in logp.shape)
+    R = B * group
+    if state_in.dtype != torch.float64 or tuple(state_in.shape) != (R, Tmax, 2):
+        raise TypeError(f"{name}: state_in must be a float64 ({R}, {Tmax}, 2) tensor (got {state_in.dtype}, {tuple(state_in.shape)})")
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ts[1:]) or hyp_len.shape != (R,) or last_tok.shape != (R,) \
+            or cand.dim() != 2 or cand.shape[0] != R:
+        raise TypeError(f"{name}: hyp_len ({R}), last_tok ({R}) and cand ({R}, C) must be integer tensors")
+    C = int(cand.shape[1])
+    if not 1 <= C <= 64:
+        raise ValueError(f"{name}: {C} candidates per hypothesis outside 1..64")
+    dev = logp.device
+    psi = torch.empty(R, C, dtype=torch.float64, device=dev)
+    if states and cand_state is None:
+        cand_state = torch.empty(R, Tmax, C, 2, dtype=torch.float64, device=dev)
+    elif states and (cand_state.dtype != torch.float64 or tuple(cand_state.shape) != (R, Tmax, C, 2) or not cand_state.is_cuda
+                     or not cand_state.is_contiguous()):
+        raise TypeError(f"{name}: cand_state must be a contiguous float64 ({R}, {Tmax}, {C}, 2) CUDA tensor")
+    hip.call("oe_ctc_prefix_score", logp, len32, B, Tmax, V, V, group, state_in.contiguous(), hyp_len.to(torch.int32).contiguous(),
+             last_tok.to(torch.int32).contiguous(), cand.to(torch.int32).contiguous(), C, int(blank), int(eos), psi,
+             cand_state if states else None)
+    return (psi, cand_state) if states else psi
+
+
 def topk_rows(x, k: int, log_softmax: bool = False):
     """`x.topk(k)` over the last dim - of log_softmax(x) when asked - in one kernel (asr_model.py:251, 258, 358).
     Returns (values float32, indices int64), sorted descending; ties go to the lowest index."""

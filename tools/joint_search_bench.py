@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""The joint CTC/attention beam search at the decode leg's shape (GPU box): the CTC prefix-score kernel per step, the whole
+search, and recognize at the same beam on the same batch.
+
+  python tools/joint_search_bench.py      # 64 utterances x 10 s (249 encoder frames), beam 10, 20 candidates, V 3246
+
+(i)  oe_ctc_prefix_score alone, 640 hypotheses x 20 candidates x 249 frames, on hypotheses three tokens deep (their states come
+     from the kernel itself), with and without the candidates' states.  The CTC log-probabilities are the log-softmax of random
+     logits (randn * 3, blank + 3: peaky frames with frequent blanks, as a CTC posterior has them), the candidates the top-20 of
+     random attention scores.  HIP events, median of 20 calls after 3 warm-up calls, three runs, the middle one reported.
+(ii) ASRModel.ctc_attention_beam_search (ctc_weight 0.3, and 0: the same loop without the kernel) and ASRModel.recognize on
+     bench.py's 12-layer Conformer with seeded random weights, random features, every call to its end on the host clock between
+     two device synchronisations; one warm-up round, then three alternating rounds, the middle one reported.  An untrained
+     decoder hardly ever emits <eos>, so all three run to the step limit, the encoder length: the same number of decoder steps."""
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from openeat_amd import ops  # noqa: E402
+from openeat_amd.models.asr_model import ASRModel  # noqa: E402
+from openeat_amd.utils import joint_search as js  # noqa: E402
+
+DEV = "cuda"
+V, B, SECONDS, BEAM, C = 3246, 64, 10, 10, 20
+MODEL_CONF = dict(encoder_num_blocks=12, decoder_num_blocks=3, r_decoder_num_blocks=3, d_model=256, attention_heads=4,
+                  linear_units=1024, dropout_rate=0.1, input_layer="conv2d", pos_enc_layer_type="rel_pos",
+                  activation_type="swish", macaron_style=True, use_cnn_module=True, cnn_module_kernel=15, causal=False,
+                  ctc_weight=0.3, lsm_weight=0.1, reverse_weight=0.3, length_normalized_loss=False)      # bench.py's
+
+
+def timed(fn, n=20):
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for i in range(n + 3):
+        if i >= 3:
+            ev[i - 3][0].record()
+        fn()
+        if i >= 3:
+            ev[i - 3][1].record()
+    torch.cuda.synchronize()
+    return sorted(a.elapsed_time(b) * 1e3 for a, b in ev)[n // 2]
+
+
+def kernel_leg(T):
+    g = torch.Generator().manual_seed(11)
+    logits = torch.randn(B, T, V, generator=g) * 3.0
+    logits[:, :, 0] += 3.0
+    logp = ops.log_softmax_rows(logits.to(DEV))
+    lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
+    R = B * BEAM
+    att = ops.log_softmax_rows((torch.randn(4, R, V, generator=g) * 3.0).to(DEV))
+    st = js.initial_state(logp, lens, BEAM, 0.3)
+    for d in range(3):
+        st = js.search_step(logp, lens, st, att[d], BEAM, C, V - 1, 0.3, 0.0)
+    _, cand = ops.topk_rows(att[3], C)
+    last = st.tokens[:, -1].contiguous()
+    hyp_len = st.length.to(torch.int32)
+    cand_state = torch.empty(R, T, C, 2, dtype=torch.float64, device=DEV)
+    live = int(((st.total > -float("inf")) & ~st.finished).sum())
+    print(f"(i) oe_ctc_prefix_score: {R} hypotheses ({live} live, {int(st.length.max())} tokens deep) x {C} candidates x {T} frames, V {V}")
+    runs = {"with states": [], "psi only": []}
+    for _ in range(3):
+        runs["with states"].append(timed(lambda: ops.ctc_prefix_score(logp, lens, st.state, hyp_len, last, cand, V - 1, group=BEAM,
+                                                                      cand_state=cand_state)))
+        runs["psi only"].append(timed(lambda: ops.ctc_prefix_score(logp, lens, st.state, hyp_len, last, cand, V - 1, group=BEAM,
+                                                                   states=False)))
+    for name, r in runs.items():
+        mid = sorted(r)[1]
+        print(f"  {name}: {mid:8.1f} us per step = {mid * 1e3 / T:6.1f} ns per frame (runs {', '.join('%.1f' % x for x in r)})")
+    print(f"  states written per step: {R * T * C * 16 / 2 ** 20:.1f} MiB")
+
+
+def search_leg():
+    torch.manual_seed(7)
+    model = ASRModel(80, V, **MODEL_CONF).to(DEV).eval()
+    g = torch.Generator().manual_seed(123)
+    feats = torch.randn(B, SECONDS * 100 - 2, 80, generator=g).to(DEV)
+    flen = torch.full((B,), feats.shape[1], dtype=torch.int32, device=DEV)
+    out = {}
+
+    def wall(name, fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out[name] = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    legs = {"joint search, ctc_weight 0.3": lambda: model.ctc_attention_beam_search(feats, flen, BEAM, 0.3, ctc_candidates=C),
+            "joint search, ctc_weight 0  ": lambda: model.ctc_attention_beam_search(feats, flen, BEAM, 0.0, ctc_candidates=C),
+            "recognize                   ": lambda: model.recognize(feats, flen, BEAM).tolist()}
+    runs = {k: [] for k in legs}
+    with torch.no_grad():
+        for it in range(4):
+            for name, fn in legs.items():
+                t = wall(name, fn)
+                if it:
+                    runs[name].append(t)
+    steps = model._encode(feats, flen)[0].shape[1]
+    print(f"(ii) {B} utterances x {SECONDS} s = {steps} encoder frames = decoder steps, beam {BEAM}, {C} candidates")
+    mids = {}
+    for name, r in runs.items():
+        mids[name] = sorted(r)[1]
+        mean_len = sum(len([t for t in h if t != V - 1]) for h in out[name]) / B
+        print(f"  {name}: {mids[name] * 1e3:8.1f} ms = {mids[name] * 1e6 / steps:7.1f} us per step, mean output {mean_len:.1f} tokens "
+              f"(runs {', '.join('%.1f' % (x * 1e3) for x in r)})")
+    a, b, c = mids.values()
+    print(f"  joint (0.3) / recognize: {a / c:.2f};  joint (0) / recognize: {b / c:.2f};  the CTC side of a step: {(a - b) * 1e6 / steps:.1f} us")
+
+
+if __name__ == "__main__":
+    assert torch.cuda.is_available(), "this tool measures on the GPU"
+    kernel_leg(SECONDS * 25 - 1)
+    search_leg()
