@@ -664,15 +664,153 @@ int oe_feature_dither(float* x, const int* nframes, int B, int Tmax, int F, floa
 int oe_speed_perturb(const float* wav, long ld_in, const int* n_in, const float* speed, int B, int Nmax_out, float* out,
                      long ld_out, const int* n_out, void* stream);
 
+/* A back-off n-gram (ARPA) language model as the kernels read it (built by openeat_amd/models/ngram_lm.py, which states the
+ * layout once more):
+ *   unigrams (n_words, 2) f32 = (log10 p, back-off) by word id - every word is listed, <unk> included;
+ *   table (capacity) slots of 16 bytes {u64 key, f32 log10 p, f32 back-off}, capacity a power of two >= twice the number of
+ *     n-grams of order >= 2, open addressing with linear probing from murmur3_fmix64(key) & (capacity-1), empty key = ~0.
+ *     An n-gram's entry number is its word id (order 1) or n_words + its slot; its key is
+ *     (entry number of its first k-1 words) << 32 | id of its k-th word.  The key is the n-gram: lookups are exact.
+ *     max_probe = the longest displacement of any stored key; a lookup reads at most max_probe + 1 slots.
+ *   order 1..5; n_words + capacity < 2^31; bos_word / eos_word / unk_word the word ids of <s>, </s>, <unk>.
+ *   tok2word (V) i32: token id -> word id (the <unk> id for tokens the model does not list); a token id outside 0..V-1 and a
+ *     word id outside 0..n_words-1 count as <unk>.
+ * The struct is host memory, read during the call only; the three pointers are device pointers. */
+typedef struct oe_ngram_model {
+    const float* unigrams;
+    const void* table;
+    const int* tok2word;
+    long capacity;
+    int n_words, max_probe, order, bos_word, eos_word, unk_word, V;
+} oe_ngram_model;
+
+/* Back-off n-gram (ARPA) language-model score of R hypotheses on the device, one wavefront per hypothesis
+ * (asr_model.py:515-516: `lm.score(' '.join(content), bos=True, eos=True)` with kenlm, once per hypothesis on the host).
+ * Total log10 probability, the ARPA back-off definition: with w the word ids of [<s> if bos] tok2word[tokens[r, :len]]
+ * [</s> if eos] and h the up to order-1 words before position i (never reaching before the first word),
+ *   p(w_i | h) = logp(h w_i) if that n-gram is listed, else backoff(h) + p(w_i | h without its first word),
+ *   backoff(h) = 0 when h is not listed; <s> is context only and never scored.
+ * model: an oe_ngram_model.  tokens (R, ld) i32, lens (R) i32: lens[r] < 0 = the slot does not exist (as out_len of
+ * oe_ctc_prefix_beam); what lies behind lens[r] is never read.
+ * Outputs: score (R) f64, -inf for a missing slot;  optional tok_logp (R, ld+1) f64 and tok_order (R, ld+1) i32: the term
+ * and the matched n-gram length of token j at [r, j], of </s> at [r, len] when eos; entries behind that, and the whole
+ * row of a missing slot, are left untouched.
+ * One launch, no workspace, no atomics; float64 sums in a fixed order (bit-reproducible); capturable. */
+int oe_ngram_score(const oe_ngram_model* model, const int* tokens, long ld, const int* lens, int R, int bos, int eos,
+                   double* score, double* tok_logp, int* tok_order, void* stream);
+
+/* A context graph (the hotwords of the biased search below) as the kernel reads it - an Aho-Corasick automaton built by
+ * openeat_amd/utils/context_graph.py, which states the layout once more.  States are trie nodes, the root is 0,
+ * n_states <= 2^20:
+ *   edges (capacity) slots of 16 bytes {u64 key, i32 next state, i32 0}: the TRIE edges only, in the table format of
+ *     oe_ngram_model (open addressing, linear probing from murmur3_fmix64(key) & (capacity-1), empty key = ~0, capacity a
+ *     power of two, max_probe the longest displacement), key = state << 32 | token.  A missing edge follows fail and
+ *     tries again - depth falls with every step, so at most 32 steps and 33 probes; from the root a missing edge stays there.
+ *   fail (n_states) i32: the longest proper suffix of the state that is a trie node.
+ *   out (n_states, 2) 32-bit words = (f32 score, i32 link): the score of the phrase that ends exactly at the state (0.0
+ *     if none does) and the nearest state on its fail chain at which a phrase ends (0: none).  The phrases that end at a
+ *     position are kept as this LIST, longest first, and added one by one - a pre-summed value would not reproduce the
+ *     float64 sum of hits(p) below.
+ *   pend (n_states) i32: the depth of the first state on the chain s, fail[s], .. that has children, which is k(p).
+ *   c: the per-token partial credit, finite and >= 0.
+ * The struct is host memory, read during the call only; the four pointers are device pointers. */
+typedef struct oe_context_graph {
+    const void* edges;
+    const int* fail;
+    const void* out;
+    const int* pend;
+    long capacity;
+    int max_probe, n_states;
+    float c;
+} oe_context_graph;
+
 /* CTC prefix beam search on the device, one wavefront per utterance (asr_model.py:359-396; the host functions below are
- * the same algorithm on the CPU and serve as its checker).  topk_logp (B, Tmax, beam) f32 and topk_idx (B, Tmax, beam) i64
- * as oe_topk_rows writes them; lens (B) i32 valid frames per utterance or NULL; beam <= 16.  workspace:
- * oe_ctc_prefix_beam_workspace_bytes(B, Tmax, beam) bytes of device memory whose LAST 4-byte word the caller zeroes and
- * reads back after the stream has drained (non-zero: a prefix exceeded max_len).  Outputs, device memory: out_prefix
- * (B, beam, max_len) i32, out_len (B, beam) i32 (-1: fewer than `beam` prefixes exist), out_score (B, beam) f64. */
+ * the same algorithm on the CPU and serve as its checker): plain, with n-gram LM shallow fusion (lm != NULL), with hotword
+ * biasing (ctx != NULL), or with both.  One entry point, one argument struct, four instantiations of one kernel:
+ *   lm NULL, ctx NULL: the plain search;  lm set, ctx NULL: the LM-fused search;
+ *   lm NULL, ctx set:  the biased search without an LM;  lm set, ctx set: the biased search with the LM.
+ *
+ * The plain search.  topk_logp (B, Tmax, beam) f32 and topk_idx (B, Tmax, beam) i64 as oe_topk_rows writes them; lens (B)
+ * i32 valid frames per utterance or NULL; beam <= 16.  workspace: oe_ctc_prefix_beam_workspace_bytes(B, Tmax, beam) bytes of
+ * device memory whose LAST 4-byte word the caller zeroes and reads back after the stream has drained (non-zero: a prefix
+ * exceeded max_len); the same for every variant.  Outputs, device memory: out_prefix (B, beam, max_len) i32, out_len (B, beam)
+ * i32 (-1: fewer than `beam` prefixes exist), out_score (B, beam) f64 = log_add(pb, pnb), in the search's own order (no
+ * re-sort).  out_ctc, out_lm and out_bias are neither required nor written; eos and final are not read.  lm_weight and
+ * length_bonus must be 0: the plain search has no such terms, and a non-zero one is reported, not ignored.
+ *
+ * With n-gram LM shallow fusion (lm != NULL).  These are the semantics every layer refers to.  It is the algorithm of the
+ * plain search (asr_model.py:359-396) with one change, the key that orders next_hyps before the cut to `beam`:
+ *   total(p) = log_add(pb, pnb) + lm_weight * LM(p) + length_bonus * len(p)
+ *   LM(p)    = sum over i < len(p), left to right in float64, of log10 p(word(p_i) | h_i)
+ * LM terms: p(w | h) is the ARPA back-off definition exactly as oe_ngram_score states it - h the up to order-1 previous
+ *   words, starting from <s>, which is context only and never scored; token -> word through tok2word; out-of-range ids count
+ *   as <unk>.  So LM(p) is oe_ngram_score(p, bos=1, eos=0) up to summation order.
+ * Units: log10, mixed in unconverted, as the reference and the rescoring do with kenlm's numbers.
+ * Per-frame updates: the pb / pnb updates are unchanged, the same arithmetic in the same visiting order; the CTC numbers
+ *   are the same bits as the plain search's.
+ * Sort order: stable and descending by total, so ties keep insertion order (the first-touch stamp).
+ * LM(p) depends on the prefix only: the two routes that merge into one prefix carry the same value and the same LM state.
+ * End of the utterance: if eos, every surviving prefix gets LM += log10 p(</s> | its context); the <= beam survivors are
+ *   stably re-sorted by total.  An utterance of zero frames yields the one empty prefix, with LM = p(</s> | <s>) when eos.
+ * Outputs per (b, slot), device memory: out_prefix (B, beam, max_len) i32 and out_len (B, beam) i32 with -1 for a missing
+ *   slot; out_score = total, out_ctc = log_add(pb, pnb), out_lm = LM including the </s> term, each (B, beam) f64 and -inf
+ *   for a missing slot; the status word of the workspace as for the plain search.
+ * Identity with zero weights: with lm_weight == 0 and length_bonus == 0 the n-best lists and their order are those of
+ *   the plain search, and out_ctc equals its out_score bit for bit.
+ * topk_logp / topk_idx / lens / beam (<= 16) / max_len / workspace as for the plain search; lm an oe_ngram_model
+ * (order <= 5); lm_weight and length_bonus finite.  Anything else, and a null pointer other than lens, is reported through
+ * oe_last_error before any launch.  One launch, no atomics other than the status word, no allocation, no host read: capturable.
+ *
+ * With hotword (contextual) biasing (ctx != NULL), with or without the n-gram LM.  These are the semantics every layer
+ * refers to.
+ * A context graph is a set of distinct phrases q, each a sequence of 1..32 token ids in 1..V-1 (never the blank) with a
+ * float32 score s(q), and one float32 per-token partial credit c >= 0; by default s(q) = c * len(q) in float32.  For a
+ * token prefix p:
+ *   hits(p) = the sum of s(q) over every occurrence of every phrase in p, an occurrence being a pair (i, q) with
+ *             p[i-len(q):i] == q, 1 <= i <= len(p); overlapping and nested occurrences all count.  The float32 values are
+ *             added in float64 in order of increasing i, within one i the longest phrase first.
+ *   k(p)    = the largest k <= len(p) such that the last k tokens of p are a PROPER prefix of some phrase (strictly
+ *             shorter than it); 0 if there is none.
+ *   bias(p) = hits(p) + (double)c * k(p) during the search; at the end of the utterance, with `final` set, the pending
+ *             credit is dropped: bias(p) = hits(p).
+ * Partial credit keeps a half-spoken hotword in the beam; it is taken back when the phrase fails and at the end of the audio.
+ * The search is the LM-fused one with one more summand, products and sums each rounded on their own:
+ *   total(p) = ((log_add(pb, pnb) + lm_weight * LM(p)) + length_bonus * len(p)) + bias(p)
+ *   without an LM (lm == NULL):  total(p) = (log_add(pb, pnb) + length_bonus * len(p)) + bias(p).
+ * The pb / pnb updates, the visiting order, the first-touch stamps and the stable descending sort are unchanged.  bias(p)
+ * depends on the prefix only: two routes that merge into one prefix carry the same value and the same automaton state.
+ * End of the utterance: (1) the </s> LM term if an LM is given and eos; (2) the pending credit dropped if final; (3) the
+ * survivors stably re-sorted by total.  An utterance of zero frames yields the one empty prefix with bias 0.
+ * Identities: with an empty graph, and with one whose scores and c are all zero, the n-best lists, their order, out_ctc,
+ *   out_lm and out_score are bit for bit those of the LM-fused search with the same LM arguments; without an LM and with
+ *   length_bonus == 0 the lists and out_ctc are bit for bit those of the plain search.
+ * Arguments: those of the LM-fused search, ctx (an oe_context_graph), final, out_bias (B, beam) f64 = bias as it entered
+ * out_score, -inf for a missing slot.  lm == NULL means no LM: out_lm may then be NULL, lm_weight and eos are ignored and
+ * out_lm is not written.  Checked before any launch and reported through oe_last_error: null pointers (args, the model's and
+ * the graph's among them), beam 1..16, non-finite weights or c, c < 0, the model checks of the LM-fused search, n_states
+ * 1..2^20, a power-of-two capacity of the graph, its max_probe.  One launch, no atomics other than the status word, no
+ * allocation, no host read: capturable.
+ *
+ * The structs are host memory, read during the call only: the launch copies what the kernel takes. */
+typedef struct oe_prefix_beam_args {
+    const float* topk_logp;
+    const long long* topk_idx;
+    const int* lens;              /* NULL: every utterance has Tmax frames */
+    int B, Tmax, beam, max_len;
+    const oe_ngram_model* lm;     /* NULL: no LM */
+    const oe_context_graph* ctx;  /* NULL: no graph */
+    double lm_weight, length_bonus;
+    int eos, final;               /* eos: read only with an LM; final: read only with a graph */
+    void* workspace;
+    int* out_prefix;
+    int* out_len;
+    double* out_score;
+    double* out_ctc;              /* with an LM or a graph */
+    double* out_lm;               /* with an LM */
+    double* out_bias;             /* with a graph */
+} oe_prefix_beam_args;
 size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam);
-int oe_ctc_prefix_beam(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam, int max_len,
-                       void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream);
+int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream);
 /* CTC prefix beam search, HOST code (all pointers are host pointers): the per-frame recursion of
  * asr_model.py:359-396 on the top-`beam` (log-prob, token) pairs of every frame (computed on the
  * device).  Doubles and insertion-ordered stable pruning as in the reference's Python, so the
@@ -685,112 +823,6 @@ int oe_ctc_prefix_beam_host(const float* topk_logp_host, const long long* topk_i
 int oe_ctc_prefix_beam_host_batch(const float* topk_logp_host, const long long* topk_idx_host, int B, int Tmax,
                                   const int* lens_host, int beam, int max_len, int* out_prefix_host, int* out_len_host,
                                   double* out_score_host, int n_threads);
-
-/* Back-off n-gram (ARPA) language-model score of R hypotheses on the device, one wavefront per hypothesis
- * (asr_model.py:515-516: `lm.score(' '.join(content), bos=True, eos=True)` with kenlm, once per hypothesis on the host).
- * Total log10 probability, the ARPA back-off definition: with w the word ids of [<s> if bos] tok2word[tokens[r, :len]]
- * [</s> if eos] and h the up to order-1 words before position i (never reaching before the first word),
- *   p(w_i | h) = logp(h w_i) if that n-gram is listed, else backoff(h) + p(w_i | h without its first word),
- *   backoff(h) = 0 when h is not listed; <s> is context only and never scored.
- * The model (built by openeat_amd/models/ngram_lm.py, which states the layout once more):
- *   unigrams (n_words, 2) f32 = (log10 p, back-off) by word id - every word is listed, <unk> included;
- *   table (capacity) slots of 16 bytes {u64 key, f32 log10 p, f32 back-off}, capacity a power of two >= twice the number of
- *     n-grams of order >= 2, open addressing with linear probing from murmur3_fmix64(key) & (capacity-1), empty key = ~0.
- *     An n-gram's entry number is its word id (order 1) or n_words + its slot; its key is
- *     (entry number of its first k-1 words) << 32 | id of its k-th word.  The key is the n-gram: lookups are exact.
- *     max_probe = the longest displacement of any stored key; a lookup reads at most max_probe + 1 slots.
- *   order 1..5; n_words + capacity < 2^31.
- * tok2word (V) i32: token id -> word id (the <unk> id for tokens the model does not list); a token id outside 0..V-1 and a
- * word id outside 0..n_words-1 count as <unk>.  tokens (R, ld) i32, lens (R) i32: lens[r] < 0 = the slot does not exist (as
- * out_len of oe_ctc_prefix_beam); what lies behind lens[r] is never read.
- * Outputs: score (R) f64, -inf for a missing slot;  optional tok_logp (R, ld+1) f64 and tok_order (R, ld+1) i32: the term
- * and the matched n-gram length of token j at [r, j], of </s> at [r, len] when eos; entries behind that, and the whole
- * row of a missing slot, are left untouched.
- * One launch, no workspace, no atomics; float64 sums in a fixed order (bit-reproducible); capturable. */
-int oe_ngram_score(const float* unigrams, int n_words, const void* table, long capacity, int max_probe, int order,
-                   int bos_word, int eos_word, int unk_word, const int* tok2word, int V, const int* tokens, long ld,
-                   const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order, void* stream);
-
-/* CTC prefix beam search with n-gram LM shallow fusion on the device, one wavefront per utterance.  These are the semantics
- * every layer refers to.  It is the algorithm of oe_ctc_prefix_beam (asr_model.py:359-396) with one change, the key that
- * orders next_hyps before the cut to `beam`:
- *   total(p) = log_add(pb, pnb) + lm_weight * LM(p) + length_bonus * len(p)
- *   LM(p)    = sum over i < len(p), left to right in float64, of log10 p(word(p_i) | h_i)
- * LM terms: p(w | h) is the ARPA back-off definition exactly as oe_ngram_score states it - h the up to order-1 previous
- *   words, starting from <s>, which is context only and never scored; token -> word through tok2word; out-of-range ids count
- *   as <unk>.  So LM(p) is oe_ngram_score(p, bos=1, eos=0) up to summation order.
- * Units: log10, mixed in unconverted, as the reference and the rescoring do with kenlm's numbers.
- * Per-frame updates: the pb / pnb updates are unchanged, the same arithmetic in the same visiting order; the CTC numbers
- *   are the same bits as oe_ctc_prefix_beam's.
- * Sort order: stable and descending by total, so ties keep insertion order (the first-touch stamp).
- * LM(p) depends on the prefix only: the two routes that merge into one prefix carry the same value and the same LM state.
- * End of the utterance: if eos, every surviving prefix gets LM += log10 p(</s> | its context); the <= beam survivors are
- *   stably re-sorted by total.  An utterance of zero frames yields the one empty prefix, with LM = p(</s> | <s>) when eos.
- * Outputs per (b, slot), device memory: out_prefix (B, beam, max_len) i32 and out_len (B, beam) i32 with -1 for a missing
- *   slot; out_score = total, out_ctc = log_add(pb, pnb), out_lm = LM including the </s> term, each (B, beam) f64 and -inf
- *   for a missing slot; the status word of the workspace as for oe_ctc_prefix_beam.
- * Identity with zero weights: with lm_weight == 0 and length_bonus == 0 the n-best lists and their order are those of
- *   oe_ctc_prefix_beam, and out_ctc equals its out_score bit for bit.
- * topk_logp / topk_idx / lens / beam (<= 16) / max_len / workspace (oe_ctc_prefix_beam_lm_workspace_bytes bytes, last word
- * zeroed by the caller) as for oe_ctc_prefix_beam; unigrams .. V the model arguments of oe_ngram_score (order <= 5);
- * lm_weight and length_bonus finite.  Anything else, and a null pointer other than lens, is reported through oe_last_error
- * before any launch.  One launch, no atomics other than the status word, no allocation, no host read: capturable. */
-size_t oe_ctc_prefix_beam_lm_workspace_bytes(int B, int Tmax, int beam);
-int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                          int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
-                          int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, double lm_weight,
-                          double length_bonus, int eos, void* workspace, int* out_prefix, int* out_len, double* out_score,
-                          double* out_ctc, double* out_lm, void* stream);
-
-/* CTC prefix beam search with hotword (contextual) biasing on the device, one wavefront per utterance, with or without the
- * n-gram LM.  These are the semantics every layer refers to.
- * A context graph is a set of distinct phrases q, each a sequence of 1..32 token ids in 1..V-1 (never the blank) with a
- * float32 score s(q), and one float32 per-token partial credit c >= 0; by default s(q) = c * len(q) in float32.  For a
- * token prefix p:
- *   hits(p) = the sum of s(q) over every occurrence of every phrase in p, an occurrence being a pair (i, q) with
- *             p[i-len(q):i] == q, 1 <= i <= len(p); overlapping and nested occurrences all count.  The float32 values are
- *             added in float64 in order of increasing i, within one i the longest phrase first.
- *   k(p)    = the largest k <= len(p) such that the last k tokens of p are a PROPER prefix of some phrase (strictly
- *             shorter than it); 0 if there is none.
- *   bias(p) = hits(p) + (double)c * k(p) during the search; at the end of the utterance, with `final` set, the pending
- *             credit is dropped: bias(p) = hits(p).
- * Partial credit keeps a half-spoken hotword in the beam; it is taken back when the phrase fails and at the end of the audio.
- * The search is oe_ctc_prefix_beam_lm's with one more summand, products and sums each rounded on their own:
- *   total(p) = ((log_add(pb, pnb) + lm_weight * LM(p)) + length_bonus * len(p)) + bias(p)
- *   without an LM (unigrams == NULL):  total(p) = (log_add(pb, pnb) + length_bonus * len(p)) + bias(p).
- * The pb / pnb updates, the visiting order, the first-touch stamps and the stable descending sort are unchanged.  bias(p)
- * depends on the prefix only: two routes that merge into one prefix carry the same value and the same automaton state.
- * End of the utterance: (1) the </s> LM term if an LM is given and eos; (2) the pending credit dropped if final; (3) the
- * survivors stably re-sorted by total.  An utterance of zero frames yields the one empty prefix with bias 0.
- * Identities: with an empty graph, and with one whose scores and c are all zero, the n-best lists, their order, out_ctc,
- *   out_lm and out_score are bit for bit those of oe_ctc_prefix_beam_lm with the same LM arguments; without an LM and with
- *   length_bonus == 0 the lists and out_ctc are bit for bit those of oe_ctc_prefix_beam.
- * The graph as the kernel reads it - an Aho-Corasick automaton built by openeat_amd/utils/context_graph.py, which states the
- * layout once more.  States are trie nodes, the root is 0, n_states <= 2^20:
- *   ctx_edges (ctx_capacity) slots of 16 bytes {u64 key, i32 next state, i32 0}: the TRIE edges only, in the table format of
- *     oe_ngram_score (open addressing, linear probing from murmur3_fmix64(key) & (capacity-1), empty key = ~0, capacity a
- *     power of two, ctx_max_probe the longest displacement), key = state << 32 | token.  A missing edge follows ctx_fail and
- *     tries again - depth falls with every step, so at most 32 steps and 33 probes; from the root a missing edge stays there.
- *   ctx_fail (n_states) i32: the longest proper suffix of the state that is a trie node.
- *   ctx_out (n_states, 2) 32-bit words = (f32 score, i32 link): the score of the phrase that ends exactly at the state (0.0
- *     if none does) and the nearest state on its fail chain at which a phrase ends (0: none).  The phrases that end at a
- *     position are kept as this LIST, longest first, and added one by one - a pre-summed value would not reproduce the
- *     float64 sum above.
- *   ctx_pend (n_states) i32: the depth of the first state on the chain s, fail[s], .. that has children, which is k(p).
- * Arguments: those of oe_ctc_prefix_beam_lm, the graph, final, out_bias (B, beam) f64 = bias as it entered out_score, -inf
- * for a missing slot.  unigrams == NULL means no LM: table, tok2word and out_lm may then be NULL, lm_weight is ignored and
- * out_lm is not written.  Checked before any launch and reported through oe_last_error: null pointers, beam 1..16,
- * non-finite weights or c, c < 0, the model checks of oe_ctc_prefix_beam_lm, n_states 1..2^20, a power-of-two ctx_capacity,
- * ctx_max_probe.  workspace: oe_ctc_prefix_beam_ctx_workspace_bytes bytes, last word zeroed by the caller, as for
- * oe_ctc_prefix_beam.  One launch, no atomics other than the status word, no allocation, no host read: capturable. */
-size_t oe_ctc_prefix_beam_ctx_workspace_bytes(int B, int Tmax, int beam);
-int oe_ctc_prefix_beam_ctx(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                           int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
-                           int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, double lm_weight,
-                           double length_bonus, int eos, const void* ctx_edges, long ctx_capacity, int ctx_max_probe,
-                           const int* ctx_fail, const void* ctx_out, const int* ctx_pend, int ctx_n_states, float ctx_c,
-                           int final, void* workspace, int* out_prefix, int* out_len, double* out_score, double* out_ctc,
-                           double* out_lm, double* out_bias, void* stream);
 
 /* Batched edit distance on the device, one wavefront per pair: the counts behind the reference's error-rate table
  * (tools/compute-wer.py, Calculator.calculate) and optionally the alignment.  These are the semantics every layer refers to.

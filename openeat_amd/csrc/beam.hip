@@ -1,6 +1,6 @@
 // CTC prefix beam search on the device, one wavefront per utterance, plain, with n-gram LM shallow fusion and with hotword
-// biasing: one kernel source, template <bool LM, bool CTX>, three entry points (oe_ctc_prefix_beam, oe_ctc_prefix_beam_lm,
-// oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h).
+// biasing: one kernel source, template <bool LM, bool CTX>, one entry point (oe_ctc_prefix_beam: its oe_prefix_beam_args name
+// the n-gram model and the context graph, or neither; semantics in include/openeat_hip.h).
 // (the reference's openeat/models/asr_model.py:359-396: the per-frame Python dict loop).
 //
 // Same arithmetic and the same ordering as the reference and as the host implementation (beam_host.cpp, which stays as
@@ -466,86 +466,57 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
 static size_t pb_hist_words(int B, int Tmax, int beam) { return (size_t)B * (size_t)max(Tmax, 1) * (size_t)beam * 2; }
 
 extern "C" size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
-extern "C" size_t oe_ctc_prefix_beam_lm_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
-extern "C" size_t oe_ctc_prefix_beam_ctx_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
 
-// fn: the entry point, for its messages
-static int pb_check_shape(const char* fn, int B, int Tmax, int max_len, int beam) {
-    OE_REQUIRE(B > 0 && Tmax >= 0 && max_len >= 0, "%s: bad shape B=%d Tmax=%d max_len=%d", fn, B, Tmax, max_len);
-    OE_REQUIRE(beam >= 1 && beam <= PB_MAXBEAM, "%s: beam must be 1..%d (got %d)", fn, PB_MAXBEAM, beam);
-    return 0;
-}
-
+// la: a PbCtxArgs; the two instantiations without a graph take its PbLmArgs part
 template <bool LM, bool CTX>
-static int pb_launch(const char* name, const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                     int max_len, const typename PbArgsOf<CTX>::type& la, void* workspace, int* out_prefix, int* out_len,
-                     double* out_score, void* stream) {
-    int* hist = (int*)workspace;
-    int* status = hist + pb_hist_words(B, Tmax, beam);            // the caller zeroes this word and reads it back
-    hipLaunchKernelGGL((ctc_prefix_beam_kernel<LM, CTX>), dim3(B), dim3(64), 0, (hipStream_t)stream, topk_logp, topk_idx, Tmax, lens, beam,
-                       max_len, la, hist, out_prefix, out_len, out_score, status);
-    OE_LAUNCH_CHECK(name);
+static int pb_launch(const oe_prefix_beam_args& a, const typename PbArgsOf<CTX>::type& la, void* stream) {
+    int* hist = (int*)a.workspace;
+    int* status = hist + pb_hist_words(a.B, a.Tmax, a.beam);      // the caller zeroes this word and reads it back
+    hipLaunchKernelGGL((ctc_prefix_beam_kernel<LM, CTX>), dim3(a.B), dim3(64), 0, (hipStream_t)stream, a.topk_logp, a.topk_idx, a.Tmax, a.lens,
+                       a.beam, a.max_len, la, hist, a.out_prefix, a.out_len, a.out_score, status);
+    OE_LAUNCH_CHECK("ctc_prefix_beam");
     return 0;
 }
 
-extern "C" int oe_ctc_prefix_beam(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                                  int max_len, void* workspace, int* out_prefix, int* out_len, double* out_score, void* stream) {
-    OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score, "oe_ctc_prefix_beam: null pointer");
-    if (pb_check_shape("oe_ctc_prefix_beam", B, Tmax, max_len, beam)) return -1;
-    return pb_launch<false, false>("ctc_prefix_beam", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, PbLmArgs{}, workspace, out_prefix,
-                                   out_len, out_score, stream);
-}
-
-extern "C" int oe_ctc_prefix_beam_lm(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                                     int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
-                                     int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V,
-                                     double lm_weight, double length_bonus, int eos, void* workspace, int* out_prefix, int* out_len,
-                                     double* out_score, double* out_ctc, double* out_lm, void* stream) {
-    const char* fn = "oe_ctc_prefix_beam_lm";
-    OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score && out_ctc && out_lm, "%s: null pointer", fn);
-    OE_REQUIRE(unigrams && table && tok2word, "%s: null pointer (model)", fn);
-    if (pb_check_shape(fn, B, Tmax, max_len, beam)) return -1;
-    PbLmArgs la{};
-    if (ng_model_args(fn, unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &la.m)) return -1;
-    OE_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", fn, V);
-    OE_REQUIRE(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight and length_bonus must be finite", fn);
-    la.lm_weight = lm_weight; la.length_bonus = length_bonus; la.eos = eos; la.out_ctc = out_ctc; la.out_lm = out_lm;
-    return pb_launch<true, false>("ctc_prefix_beam_lm", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix, out_len,
-                                  out_score, stream);
-}
-
-extern "C" int oe_ctc_prefix_beam_ctx(const float* topk_logp, const long long* topk_idx, int B, int Tmax, const int* lens, int beam,
-                                      int max_len, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
-                                      int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V,
-                                      double lm_weight, double length_bonus, int eos, const void* ctx_edges, long ctx_capacity,
-                                      int ctx_max_probe, const int* ctx_fail, const void* ctx_out, const int* ctx_pend,
-                                      int ctx_n_states, float ctx_c, int final, void* workspace, int* out_prefix, int* out_len,
-                                      double* out_score, double* out_ctc, double* out_lm, double* out_bias, void* stream) {
-    const char* fn = "oe_ctc_prefix_beam_ctx";
-    OE_REQUIRE(topk_logp && topk_idx && workspace && out_prefix && out_len && out_score && out_ctc && out_bias, "%s: null pointer", fn);
-    OE_REQUIRE(ctx_edges && ctx_fail && ctx_out && ctx_pend, "%s: null pointer (context graph)", fn);
-    if (pb_check_shape(fn, B, Tmax, max_len, beam)) return -1;
+extern "C" int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream) {
+    const char* fn = "oe_ctc_prefix_beam";
+    OE_REQUIRE(args, "%s: null pointer (args)", fn);
+    const oe_prefix_beam_args& a = *args;
+    const oe_ngram_model* lm = a.lm;
+    const oe_context_graph* g = a.ctx;
+    OE_REQUIRE(a.topk_logp && a.topk_idx && a.workspace && a.out_prefix && a.out_len && a.out_score, "%s: null pointer", fn);
+    OE_REQUIRE((!lm && !g) || a.out_ctc, "%s: null pointer (out_ctc)", fn);
+    OE_REQUIRE(!lm || a.out_lm, "%s: null pointer (out_lm)", fn);
+    OE_REQUIRE(!g || a.out_bias, "%s: null pointer (out_bias)", fn);
+    OE_REQUIRE(!lm || (lm->unigrams && lm->table && lm->tok2word), "%s: null pointer (model)", fn);
+    OE_REQUIRE(!g || (g->edges && g->fail && g->out && g->pend), "%s: null pointer (context graph)", fn);
+    OE_REQUIRE(a.B > 0 && a.Tmax >= 0 && a.max_len >= 0, "%s: bad shape B=%d Tmax=%d max_len=%d", fn, a.B, a.Tmax, a.max_len);
+    OE_REQUIRE(a.beam >= 1 && a.beam <= PB_MAXBEAM, "%s: beam must be 1..%d (got %d)", fn, PB_MAXBEAM, a.beam);
     PbCtxArgs la{};
-    if (unigrams) {
-        OE_REQUIRE(table && tok2word && out_lm, "%s: null pointer (model)", fn);
-        if (ng_model_args(fn, unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &la.m)) return -1;
-        OE_REQUIRE(V > 0, "%s: bad vocabulary size V=%d", fn, V);
-        OE_REQUIRE(isfinite(lm_weight), "%s: lm_weight must be finite", fn);
-        la.lm_weight = lm_weight; la.eos = eos; la.out_lm = out_lm;
+    if (lm) {
+        if (ng_model_args(fn, lm, &la.m)) return -1;
+        OE_REQUIRE(lm->V > 0, "%s: bad vocabulary size V=%d", fn, lm->V);
+        OE_REQUIRE(isfinite(a.lm_weight), "%s: lm_weight must be finite", fn);
+        la.lm_weight = a.lm_weight; la.eos = a.eos; la.out_lm = a.out_lm;
     }
-    OE_REQUIRE(isfinite(length_bonus), "%s: length_bonus must be finite", fn);
-    OE_REQUIRE(ctx_n_states >= 1 && ctx_n_states <= (1 << 20), "%s: n_states must be 1..2^20 (got %d)", fn, ctx_n_states);
-    OE_REQUIRE(ctx_capacity >= 2 && (ctx_capacity & (ctx_capacity - 1)) == 0, "%s: the graph's capacity must be a power of two >= 2 (got %ld)",
-               fn, ctx_capacity);
-    OE_REQUIRE(ctx_max_probe >= 0 && ctx_max_probe < ctx_capacity, "%s: bad max_probe %d of the graph", fn, ctx_max_probe);
-    OE_REQUIRE(isfinite(ctx_c) && ctx_c >= 0.f, "%s: the partial credit c must be finite and >= 0", fn);
-    la.length_bonus = length_bonus; la.out_ctc = out_ctc;
-    la.edges = (const uint4*)ctx_edges; la.edge_mask = (unsigned long long)(ctx_capacity - 1); la.edge_max_probe = ctx_max_probe;
-    la.fail = ctx_fail; la.out = (const int2*)ctx_out; la.pend = ctx_pend; la.n_states = ctx_n_states; la.c = ctx_c;
-    la.final = final; la.out_bias = out_bias;
-    if (unigrams)
-        return pb_launch<true, true>("ctc_prefix_beam_ctx", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix,
-                                     out_len, out_score, stream);
-    return pb_launch<false, true>("ctc_prefix_beam_ctx", topk_logp, topk_idx, B, Tmax, lens, beam, max_len, la, workspace, out_prefix,
-                                  out_len, out_score, stream);
+    if (lm || g) {
+        OE_REQUIRE(isfinite(a.length_bonus), "%s: length_bonus must be finite", fn);
+        la.length_bonus = a.length_bonus; la.out_ctc = a.out_ctc;
+    } else {
+        OE_REQUIRE(a.lm_weight == 0.0 && a.length_bonus == 0.0,
+                   "%s: the plain search has no lm_weight or length_bonus term (got %g and %g): both must be 0", fn, a.lm_weight, a.length_bonus);
+    }
+    if (g) {
+        OE_REQUIRE(g->n_states >= 1 && g->n_states <= (1 << 20), "%s: n_states must be 1..2^20 (got %d)", fn, g->n_states);
+        OE_REQUIRE(g->capacity >= 2 && (g->capacity & (g->capacity - 1)) == 0, "%s: the graph's capacity must be a power of two >= 2 (got %ld)",
+                   fn, g->capacity);
+        OE_REQUIRE(g->max_probe >= 0 && g->max_probe < g->capacity, "%s: bad max_probe %d of the graph", fn, g->max_probe);
+        OE_REQUIRE(isfinite(g->c) && g->c >= 0.f, "%s: the partial credit c must be finite and >= 0", fn);
+        la.edges = (const uint4*)g->edges; la.edge_mask = (unsigned long long)(g->capacity - 1); la.edge_max_probe = g->max_probe;
+        la.fail = g->fail; la.out = (const int2*)g->out; la.pend = g->pend; la.n_states = g->n_states; la.c = g->c;
+        la.final = a.final; la.out_bias = a.out_bias;
+    }
+    if (!lm && !g) return pb_launch<false, false>(a, la, stream);
+    if (!g) return pb_launch<true, false>(a, la, stream);
+    return lm ? pb_launch<true, true>(a, la, stream) : pb_launch<false, true>(a, la, stream);
 }

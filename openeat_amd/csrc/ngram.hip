@@ -128,15 +128,12 @@ __global__ __launch_bounds__(64) void ngram_score_kernel(NgModel m, const int* _
     if (lane == 0) score[r] = acc;
 }
 
-extern "C" int oe_ngram_score(const float* unigrams, int n_words, const void* table, long capacity, int max_probe, int order,
-                              int bos_word, int eos_word, int unk_word, const int* tok2word, int V, const int* tokens, long ld,
-                              const int* lens, int R, int bos, int eos, double* score, double* tok_logp, int* tok_order,
-                              void* stream) {
-    OE_REQUIRE(unigrams && table && tok2word && tokens && lens && score, "oe_ngram_score: null pointer");
+extern "C" int oe_ngram_score(const oe_ngram_model* model, const int* tokens, long ld, const int* lens, int R, int bos, int eos,
+                              double* score, double* tok_logp, int* tok_order, void* stream) {
+    OE_REQUIRE(model && model->unigrams && model->table && model->tok2word && tokens && lens && score, "oe_ngram_score: null pointer");
     NgModel m;
-    if (ng_model_args("oe_ngram_score", unigrams, n_words, table, capacity, max_probe, order, bos_word, eos_word, unk_word, tok2word, V, &m))
-        return -1;
-    OE_REQUIRE(R >= 0 && V > 0 && ld >= 0, "oe_ngram_score: bad shape R=%d V=%d ld=%ld", R, V, ld);
+    if (ng_model_args("oe_ngram_score", model, &m)) return -1;
+    OE_REQUIRE(R >= 0 && m.V > 0 && ld >= 0, "oe_ngram_score: bad shape R=%d V=%d ld=%ld", R, m.V, ld);
     if (R == 0) return 0;
     hipLaunchKernelGGL(ngram_score_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, m, tokens, ld, lens, bos, eos, score, tok_logp,
                        tok_order);

@@ -48,19 +48,19 @@ __device__ __forceinline__ int ng_word(const NgModel& m, int tok) {
     return w;
 }
 
-// Host: the checks every entry point makes on the model arguments (fn: its name, for the messages; pointers and V are the
-// caller's to check), then the arguments as the kernels take them.
-static inline int ng_model_args(const char* fn, const float* unigrams, int n_words, const void* table, long capacity, int max_probe,
-                                int order, int bos_word, int eos_word, int unk_word, const int* tok2word, int V, NgModel* m) {
-    OE_REQUIRE(order >= 1 && order <= NG_MAXORDER, "%s: order must be 1..%d (got %d)", fn, NG_MAXORDER, order);
-    OE_REQUIRE(capacity >= 2 && (capacity & (capacity - 1)) == 0, "%s: capacity must be a power of two >= 2 (got %ld)", fn, capacity);
-    OE_REQUIRE(max_probe >= 0 && max_probe < capacity, "%s: bad max_probe %d", fn, max_probe);
-    OE_REQUIRE(n_words > 0 && (long)n_words + capacity < 0x7fffffffL, "%s: n_words + capacity must stay below 2^31", fn);
-    OE_REQUIRE(bos_word >= 0 && bos_word < n_words && eos_word >= 0 && eos_word < n_words && unk_word >= 0 && unk_word < n_words,
-               "%s: <s> / </s> / <unk> ids outside the vocabulary", fn);
-    m->unigrams = (const float2*)unigrams; m->table = (const uint4*)table; m->tok2word = tok2word;
-    m->mask = (unsigned long long)(capacity - 1);
-    m->n_words = n_words; m->max_probe = max_probe; m->order = order;
-    m->bos_word = bos_word; m->eos_word = eos_word; m->unk_word = unk_word; m->V = V;
+// Host: the checks every entry point makes on an oe_ngram_model (include/openeat_hip.h; fn: the entry point's name, for the
+// messages; the struct's pointers and V are the caller's to check), then the model as the kernels take it.
+static inline int ng_model_args(const char* fn, const oe_ngram_model* a, NgModel* m) {
+    OE_REQUIRE(a->order >= 1 && a->order <= NG_MAXORDER, "%s: order must be 1..%d (got %d)", fn, NG_MAXORDER, a->order);
+    OE_REQUIRE(a->capacity >= 2 && (a->capacity & (a->capacity - 1)) == 0, "%s: capacity must be a power of two >= 2 (got %ld)", fn,
+               a->capacity);
+    OE_REQUIRE(a->max_probe >= 0 && a->max_probe < a->capacity, "%s: bad max_probe %d", fn, a->max_probe);
+    OE_REQUIRE(a->n_words > 0 && (long)a->n_words + a->capacity < 0x7fffffffL, "%s: n_words + capacity must stay below 2^31", fn);
+    OE_REQUIRE(a->bos_word >= 0 && a->bos_word < a->n_words && a->eos_word >= 0 && a->eos_word < a->n_words && a->unk_word >= 0 &&
+               a->unk_word < a->n_words, "%s: <s> / </s> / <unk> ids outside the vocabulary", fn);
+    m->unigrams = (const float2*)a->unigrams; m->table = (const uint4*)a->table; m->tok2word = a->tok2word;
+    m->mask = (unsigned long long)(a->capacity - 1);
+    m->n_words = a->n_words; m->max_probe = a->max_probe; m->order = a->order;
+    m->bos_word = a->bos_word; m->eos_word = a->eos_word; m->unk_word = a->unk_word; m->V = a->V;
     return 0;
 }

@@ -175,6 +175,29 @@ class TnProblem(C.Structure):
                 ("block_start", C.c_int), ("reserved", C.c_int)]
 
 
+class NgramModel(C.Structure):
+    """oe_ngram_model (include/openeat_hip.h); filled by ngram_model."""
+    _fields_ = [("unigrams", c_fp), ("table", c_fp), ("tok2word", c_fp), ("capacity", C.c_long), ("n_words", C.c_int),
+                ("max_probe", C.c_int), ("order", C.c_int), ("bos_word", C.c_int), ("eos_word", C.c_int), ("unk_word", C.c_int),
+                ("V", C.c_int)]
+
+
+class ContextGraph(C.Structure):
+    """oe_context_graph (include/openeat_hip.h); filled by context_graph."""
+    _fields_ = [("edges", c_fp), ("fail", c_fp), ("out", c_fp), ("pend", c_fp), ("capacity", C.c_long), ("max_probe", C.c_int),
+                ("n_states", C.c_int), ("c", C.c_float)]
+
+
+class PrefixBeamArgs(C.Structure):
+    """oe_prefix_beam_args (include/openeat_hip.h).  A struct assigned through C.pointer to lm / ctx stays referenced by this one."""
+    _fields_ = [("topk_logp", c_fp), ("topk_idx", c_fp), ("lens", c_fp),
+                ("B", C.c_int), ("Tmax", C.c_int), ("beam", C.c_int), ("max_len", C.c_int),
+                ("lm", C.POINTER(NgramModel)), ("ctx", C.POINTER(ContextGraph)),
+                ("lm_weight", C.c_double), ("length_bonus", C.c_double), ("eos", C.c_int), ("final", C.c_int),
+                ("workspace", c_fp), ("out_prefix", c_fp), ("out_len", c_fp),
+                ("out_score", c_fp), ("out_ctc", c_fp), ("out_lm", c_fp), ("out_bias", c_fp)]
+
+
 I, L, F, D, P, U64, SZ = C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
@@ -264,15 +287,10 @@ _SIGNATURES = {
     "oe_feature_dither": (I, [P, P, I, I, I, F, U64, P]),
     "oe_speed_perturb": (I, [P, L, P, P, I, I, P, L, P, P]),
     "oe_ctc_prefix_beam_workspace_bytes": (SZ, [I, I, I]),
-    "oe_ctc_prefix_beam": (I, [P, P, I, I, P, I, I, P, P, P, P, P]),
+    "oe_ctc_prefix_beam": (I, [C.POINTER(PrefixBeamArgs), P]),
     "oe_ctc_prefix_beam_host": (I, [P, P, I, I, I, P, P, P]),
     "oe_ctc_prefix_beam_host_batch": (I, [P, P, I, I, P, I, I, P, P, P, I]),
-    "oe_ngram_score": (I, [P, I, P, L, I, I, I, I, I, P, I, P, L, P, I, I, I, P, P, P, P]),
-    "oe_ctc_prefix_beam_lm_workspace_bytes": (SZ, [I, I, I]),
-    "oe_ctc_prefix_beam_lm": (I, [P, P, I, I, P, I, I, P, I, P, L, I, I, I, I, I, P, I, D, D, I, P, P, P, P, P, P, P]),
-    "oe_ctc_prefix_beam_ctx_workspace_bytes": (SZ, [I, I, I]),
-    "oe_ctc_prefix_beam_ctx": (I, [P, P, I, I, P, I, I, P, I, P, L, I, I, I, I, I, P, I, D, D, I, P, L, I, P, P, P, I, F, I, P, P, P, P, P,
-                               P, P, P]),
+    "oe_ngram_score": (I, [C.POINTER(NgramModel), P, L, P, I, I, I, P, P, P, P]),
     "oe_edit_distance_workspace_bytes": (SZ, [I, I, I]),
     "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_ctc_prefix_score_init": (I, [P, P, I, I, I, L, I, I, P, P]),
@@ -526,22 +544,47 @@ def attention_bwd(a: AttnArgs):
     check(lib().oe_attention_bwd(C.byref(a), stream()), "oe_attention_bwd")
 
 
-def _prefix_beam_buffers(name, top_logp, top_idx, beam, n_scores):
-    """The argument check and the allocations the two device prefix searches share (name: oe_<name> is the entry point) ->
-    contiguous inputs, B, T, max_len, workspace (status word zeroed), prefixes (B, beam, max_len) int32, lengths (B, beam)
-    int32, n_scores x (B, beam) float64."""
-    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
-        raise TypeError(f"{name}_device: float32 / int64 CUDA tensors required")
-    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
-    B, T = top_logp.shape[0], top_logp.shape[1]
-    ml = max(T, 1)
-    dev = top_logp.device
-    ws = torch.empty(getattr(lib(), f"oe_{name}_workspace_bytes")(B, T, beam) // 4, dtype=torch.int32, device=dev)
-    ws[-1:].zero_()
-    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
-    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    scores = [torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(n_scores)]
-    return top_logp, top_idx, B, T, ml, ws, prefixes, plen, scores
+def ngram_model(lm, device) -> NgramModel:
+    """The oe_ngram_model of `lm`, an openeat_amd.models.ngram_lm.NgramLM, with its tables on `device` (the lm keeps them, the struct keeps the lm)."""
+    uni, table, tok2word = lm.device_tables(device)
+    m = NgramModel(uni.data_ptr(), table.data_ptr(), tok2word.data_ptr(), lm.capacity, lm.n_words, lm.max_probe, lm.order,
+                   lm.bos_word, lm.eos_word, lm.unk_word, int(tok2word.shape[0]))
+    m.owner = lm                                                   # the pointers live as long as the struct
+    return m
+
+
+def context_graph(graph, device) -> ContextGraph:
+    """The oe_context_graph of `graph`, an openeat_amd.utils.context_graph.ContextGraph, with its tables on `device` (the graph
+    keeps them, the struct keeps the graph)."""
+    edges, fail, out, pend = graph.device_tables(device)
+    g = ContextGraph(edges.data_ptr(), fail.data_ptr(), out.data_ptr(), pend.data_ptr(), graph.capacity, graph.max_probe,
+                     graph.n_states, float(graph.context_score))
+    g.owner = graph                                                # the pointers live as long as the struct
+    return g
+
+
+def prefix_beam_args(top_logp, top_idx, lens, beam, max_len, ws, prefixes, plen, score, ctc=None, lms=None, bias=None, *, lm=None,
+                     ctx=None, lm_weight=0.0, length_bonus=0.0, eos=True, final=True) -> PrefixBeamArgs:
+    """oe_prefix_beam_args over tensors (lens and the outputs a variant does not take: None) and lm / ctx, an NgramModel / a
+    ContextGraph struct or None."""
+    dp = lambda t: None if t is None else t.data_ptr()
+    a = PrefixBeamArgs()
+    a.topk_logp, a.topk_idx, a.lens = top_logp.data_ptr(), top_idx.data_ptr(), dp(lens)
+    a.B, a.Tmax, a.beam, a.max_len = top_logp.shape[0], top_logp.shape[1], beam, max_len
+    if lm is not None:
+        a.lm = C.pointer(lm)
+    if ctx is not None:
+        a.ctx = C.pointer(ctx)
+    a.lm_weight, a.length_bonus, a.eos, a.final = float(lm_weight), float(length_bonus), int(bool(eos)), int(bool(final))
+    a.workspace, a.out_prefix, a.out_len = ws.data_ptr(), prefixes.data_ptr(), plen.data_ptr()
+    a.out_score, a.out_ctc, a.out_lm, a.out_bias = dp(score), dp(ctc), dp(lms), dp(bias)
+    return a
+
+
+def prefix_beam(a: PrefixBeamArgs):
+    """oe_ctc_prefix_beam on the current stream.  The launch copies the kernel's arguments: nothing of `a` has to outlive the
+    call, under stream capture either."""
+    check(lib().oe_ctc_prefix_beam(C.byref(a), stream()), "oe_ctc_prefix_beam")
 
 
 def check_prefix_beam_status(bad, name: str = "oe_ctc_prefix_beam"):
@@ -559,64 +602,65 @@ def _nbest_lists(prefixes, plen, *scores):
             for b in range(B)]
 
 
+def _prefix_beam_device(name, top_logp, top_idx, lens, beam, n_scores, raw, lm=None, graph=None, **weights):
+    """What the three device prefix searches share (name: of the caller, for its messages): the argument check, the
+    allocations - workspace (status word zeroed), prefixes (B, beam, max_len) int32, lengths (B, beam) int32, n_scores x
+    (B, beam) float64 = score [, ctc, lm [, bias]] - and the launch -> the raw tuple or the lists, as the callers document."""
+    if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
+        raise TypeError(f"{name}: float32 / int64 CUDA tensors required")
+    top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
+    B, T = top_logp.shape[0], top_logp.shape[1]
+    ml = max(T, 1)
+    dev = top_logp.device
+    ws = torch.empty(lib().oe_ctc_prefix_beam_workspace_bytes(B, T, beam) // 4, dtype=torch.int32, device=dev)
+    ws[-1:].zero_()
+    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
+    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    scores = [torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(n_scores)]
+    outs = list(scores)
+    if graph is not None and lm is None:                           # out_lm is not written without an LM: the caller gets zeros
+        scores[2].zero_()
+        outs[2] = None
+    prefix_beam(prefix_beam_args(top_logp, top_idx, lens, beam, ml, ws, prefixes, plen, *outs,
+                                 lm=None if lm is None else ngram_model(lm, dev),
+                                 ctx=None if graph is None else context_graph(graph, dev), **weights))
+    if raw:
+        return (prefixes, plen, *scores, ws[-1:])
+    check_prefix_beam_status(ws[-1], name)                         # the read drains the stream
+    return _nbest_lists(prefixes, plen, *scores)
+
+
 def ctc_prefix_beam_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, raw: bool = False):
     """top_logp (B, T, beam) float32 / top_idx (B, T, beam) int64 CUDA tensors (ops.topk_rows), lens (B) int32 CUDA or None ->
     per utterance [(prefix tuple, score)], as ctc_prefix_beam_host_batch returns them.  One kernel, one wave per
     utterance; one device-to-host copy of the n-best lists.  raw=True: no copy at all - the device tensors
     (prefixes (B, beam, T) int32, lengths (B, beam) int32 with -1 for missing entries, scores (B, beam) float64) and a
     status word tensor the caller checks after its own synchronisation."""
-    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (scores,) = _prefix_beam_buffers("ctc_prefix_beam", top_logp, top_idx, beam, 1)
-    call("oe_ctc_prefix_beam", top_logp, top_idx, B, T, lens, beam, ml, ws, prefixes, plen, scores)
-    if raw:
-        return prefixes, plen, scores, ws[-1:]
-    check_prefix_beam_status(ws[-1])                               # the read drains the stream
-    return _nbest_lists(prefixes, plen, scores)
+    return _prefix_beam_device("ctc_prefix_beam_device", top_logp, top_idx, lens, beam, 1, raw)
 
 
 def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, lm,
                               lm_weight: float, length_bonus: float = 0.0, eos: bool = True, raw: bool = False):
-    """CTC prefix beam search with n-gram LM shallow fusion (oe_ctc_prefix_beam_lm; semantics in include/openeat_hip.h): the
-    inputs of ctc_prefix_beam_device plus `lm`, an openeat_amd.models.ngram_lm.NgramLM -> per utterance
+    """CTC prefix beam search with n-gram LM shallow fusion (oe_ctc_prefix_beam with an LM; semantics in include/openeat_hip.h):
+    the inputs of ctc_prefix_beam_device plus `lm`, an openeat_amd.models.ngram_lm.NgramLM -> per utterance
     [(prefix tuple, total, ctc, lm)] sorted by total.  raw=True: no copy at all - the device tensors (prefixes (B, beam, T)
     int32, lengths (B, beam) int32 with -1 for missing entries, total / ctc / lm (B, beam) float64, -inf where missing) and
     the status word tensor the caller checks after its own synchronisation."""
-    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (total, ctc, lms) = _prefix_beam_buffers("ctc_prefix_beam_lm", top_logp, top_idx, beam, 3)
-    uni, table, tok2word = lm.device_tables(top_logp.device)
-    call("oe_ctc_prefix_beam_lm", top_logp, top_idx, B, T, lens, beam, ml, uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order,
-         lm.bos_word, lm.eos_word, lm.unk_word, tok2word, int(tok2word.shape[0]), float(lm_weight), float(length_bonus),
-         int(bool(eos)), ws, prefixes, plen, total, ctc, lms)
-    if raw:
-        return prefixes, plen, total, ctc, lms, ws[-1:]
-    check_prefix_beam_status(ws[-1], "oe_ctc_prefix_beam_lm")
-    return _nbest_lists(prefixes, plen, total, ctc, lms)
+    return _prefix_beam_device("ctc_prefix_beam_lm_device", top_logp, top_idx, lens, beam, 3, raw, lm, lm_weight=lm_weight,
+                               length_bonus=length_bonus, eos=eos)
 
 
 def ctc_prefix_beam_ctx_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, graph, lm=None,
                                lm_weight: float = 0.0, length_bonus: float = 0.0, eos: bool = True, final: bool = True,
                                raw: bool = False):
-    """CTC prefix beam search with hotword biasing (oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h): the inputs of
-    ctc_prefix_beam_device plus `graph`, an openeat_amd.utils.context_graph.ContextGraph, and optionally `lm`, an NgramLM,
-    fused as in ctc_prefix_beam_lm_device -> per utterance [(prefix tuple, total, ctc, lm, bias)] sorted by total, lm = 0.0
-    when no LM is given.  final: the pending partial credit is dropped at the end of the utterance.  raw=True: no copy at
-    all - the device tensors (prefixes, lengths, total / ctc / lm / bias (B, beam) float64, -inf where missing; lm all zero
-    without an LM) and the status word tensor the caller checks after its own synchronisation."""
-    top_logp, top_idx, B, T, ml, ws, prefixes, plen, (total, ctc, lms, bias) = _prefix_beam_buffers("ctc_prefix_beam_ctx", top_logp, top_idx,
-                                                                                                   beam, 4)
-    edges, fail, out, pend = graph.device_tables(top_logp.device)
-    if lm is None:
-        lms.zero_()
-        model = (None, 0, None, 0, 0, 0, 0, 0, 0, None, 0)
-    else:
-        uni, table, tok2word = lm.device_tables(top_logp.device)
-        model = (uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word, tok2word,
-                 int(tok2word.shape[0]))
-    call("oe_ctc_prefix_beam_ctx", top_logp, top_idx, B, T, lens, beam, ml, *model, float(lm_weight), float(length_bonus), int(bool(eos)),
-         edges, graph.capacity, graph.max_probe, fail, out, pend, graph.n_states, float(graph.context_score), int(bool(final)), ws,
-         prefixes, plen, total, ctc, None if lm is None else lms, bias)
-    if raw:
-        return prefixes, plen, total, ctc, lms, bias, ws[-1:]
-    check_prefix_beam_status(ws[-1], "oe_ctc_prefix_beam_ctx")
-    return _nbest_lists(prefixes, plen, total, ctc, lms, bias)
+    """CTC prefix beam search with hotword biasing (oe_ctc_prefix_beam with a graph; semantics in include/openeat_hip.h): the
+    inputs of ctc_prefix_beam_device plus `graph`, an openeat_amd.utils.context_graph.ContextGraph, and optionally `lm`, an
+    NgramLM, fused as in ctc_prefix_beam_lm_device -> per utterance [(prefix tuple, total, ctc, lm, bias)] sorted by total,
+    lm = 0.0 when no LM is given.  final: the pending partial credit is dropped at the end of the utterance.  raw=True: no
+    copy at all - the device tensors (prefixes, lengths, total / ctc / lm / bias (B, beam) float64, -inf where missing; lm
+    all zero without an LM) and the status word tensor the caller checks after its own synchronisation."""
+    return _prefix_beam_device("ctc_prefix_beam_ctx_device", top_logp, top_idx, lens, beam, 4, raw, lm, graph, lm_weight=lm_weight,
+                               length_bonus=length_bonus, eos=eos, final=final)
 
 
 def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, lens, beam: int, n_threads: int = 0):

@@ -360,7 +360,7 @@ class ASRModel(torch.nn.Module):
     @torch.no_grad()
     def ctc_lm_beam_search(self, features, features_length, beam_size: int, lm, lm_weight: float, length_bonus: float = 0.0,
                            eos: bool = True):
-        """CTC prefix beam search with n-gram LM shallow fusion, batched (oe_ctc_prefix_beam_lm; semantics in
+        """CTC prefix beam search with n-gram LM shallow fusion, batched (oe_ctc_prefix_beam, lm; semantics in
         include/openeat_hip.h): prefixes are pruned every frame by log_add(pb, pnb) + lm_weight * LM + length_bonus * len.
         -> per utterance [(prefix tuple, total, ctc, lm)] sorted by total.  Needs an NgramLM, the device beam and
         beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
@@ -375,7 +375,7 @@ class ASRModel(torch.nn.Module):
     @torch.no_grad()
     def ctc_context_beam_search(self, features, features_length, beam_size: int, context, lm=None, lm_weight: float = 0.0,
                                 length_bonus: float = 0.0, eos: bool = True):
-        """CTC prefix beam search with hotword biasing, batched (oe_ctc_prefix_beam_ctx; semantics in include/openeat_hip.h):
+        """CTC prefix beam search with hotword biasing, batched (oe_ctc_prefix_beam, ctx; semantics in include/openeat_hip.h):
         prefixes are pruned every frame by ctc_lm_beam_search's total (the LM term only with an NgramLM) + bias(prefix), the
         score `context`, a ContextGraph, gives the hotwords a prefix holds, plus a per-token credit while one is half spoken;
         at the end of the utterance the pending credit is dropped.  -> per utterance [(prefix tuple, total, ctc, lm, bias)]

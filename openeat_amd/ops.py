@@ -2375,15 +2375,13 @@ def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token:
     if tokens.dtype.is_floating_point or lens.dtype.is_floating_point or tokens.dim() != 2 or lens.shape != tokens.shape[:1]:
         raise TypeError("ngram_score: tokens (R, ld) and lens (R) must be integer tensors")
     dev = tokens.device
-    uni, table, tok2word = lm.device_tables(dev)
     R, ld = int(tokens.shape[0]), int(tokens.shape[1])
     tok32 = tokens.to(torch.int32).contiguous()
     len32 = lens.to(torch.int32).contiguous()
     score = torch.empty(R, dtype=torch.float64, device=dev)
     tok_logp = torch.zeros(R, ld + 1, dtype=torch.float64, device=dev) if per_token else None
     tok_order = torch.zeros(R, ld + 1, dtype=torch.int32, device=dev) if per_token else None
-    hip.call("oe_ngram_score", uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word,
-             tok2word, int(tok2word.shape[0]), tok32, ld, len32, R, int(bool(bos)), int(bool(eos)), score, tok_logp, tok_order)
+    hip.call("oe_ngram_score", hip.ngram_model(lm, dev), tok32, ld, len32, R, int(bool(bos)), int(bool(eos)), score, tok_logp, tok_order)
     return (score, tok_logp, tok_order) if per_token else score
 
 

@@ -1,5 +1,5 @@
 """Hotword (contextual) biasing for the device CTC prefix beam search: the host builder of the context graph that
-`oe_ctc_prefix_beam_ctx` reads (semantics in include/openeat_hip.h, restated here).
+`oe_ctc_prefix_beam` reads (semantics in include/openeat_hip.h, restated here).
 
 A graph is a set of distinct phrases q (1..32 token ids >= 1, never the blank), each with a float32 score s(q), and one
 float32 per-token partial credit c >= 0; by default s(q) = c * len(q) in float32.  For a token prefix p

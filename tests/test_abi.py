@@ -1,8 +1,9 @@
 """CPU: the C-ABI library loads and exports every symbol include/openeat_hip.h
-declares (no compute is launched here)."""
+declares, and the ctypes structures have the layout of its structs (no compute is launched here)."""
 import ctypes
 import os
 import re
+import subprocess
 
 from conftest import ROOT
 
@@ -30,6 +31,35 @@ def test_python_binding_covers_the_header():
     assert sorted(hip.exported_symbols()) == declared_functions()
     lib = hip.lib()
     assert lib.oe_abi_version() >= 1
+
+
+def test_ctypes_structures_have_the_layout_the_header_declares(tmp_path):
+    """Every ctypes.Structure of hip.py against its C struct: a generated host program prints sizeof and the offsetof of every
+    field named in _fields_.  The C struct of a class is the one whose name, without oe_ and underscores, is the class name in
+    lower case (GemmArgs: oe_gemm_args); the field names are the same on both sides."""
+    from openeat_amd import hip
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    c_names = {n[3:].replace("_", ""): n for n in re.findall(r"\btypedef\s+struct\s+(oe_[a-z0-9_]+)\s*\{", src)}
+    classes = {name.lower(): cls for name, cls in vars(hip).items() if isinstance(cls, type) and issubclass(cls, ctypes.Structure)
+               and cls is not ctypes.Structure}
+    assert sorted(classes) == sorted(c_names) and len(classes) >= 11, (sorted(classes), sorted(c_names))
+    for new in ("oe_ngram_model", "oe_context_graph", "oe_prefix_beam_args"):
+        assert new in c_names.values()
+    lines = ["#include <stddef.h>", "#include <stdio.h>", f'#include "{HEADER}"', "int main(void) {"]
+    want = {}
+    for key, cls in classes.items():
+        c = c_names[key]
+        lines.append(f'    printf("{c} %zu\\n", sizeof({c}));')
+        want[c] = ctypes.sizeof(cls)
+        for field, _ in cls._fields_:
+            lines.append(f'    printf("{c}.{field} %zu\\n", offsetof({c}, {field}));')
+            want[f"{c}.{field}"] = getattr(cls, field).offset
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["g++", "-std=c++17", "-o", str(tmp_path / "layout"), str(tmp_path / "layout.cpp")])
+    got = {k: int(v) for k, v in (line.split() for line in subprocess.check_output([str(tmp_path / "layout")]).decode().splitlines())}
+    assert got == want, sorted(k for k in want if got.get(k) != want[k])
+    print(f"{len(classes)} structs, {len(want)} sizes and offsets agree: {', '.join(sorted(c_names.values()))}")
 
 
 def test_invalid_arguments_are_reported_not_launched():

@@ -1,4 +1,4 @@
-"""GPU: CTC prefix beam search with hotword biasing on the device (oe_ctc_prefix_beam_ctx) against the yardstick
+"""GPU: CTC prefix beam search with hotword biasing on the device (oe_ctc_prefix_beam with a graph) against the yardstick
 (tests/ctc_bias_beam_ref.py: the dict loop with the biased key, the bias by brute force from the definition - independent of
 the product and held to what is pinned by tests/test_ctc_bias_beam_ref.py), run on the device's own top-k.
 
@@ -107,8 +107,8 @@ def _used(pre, plen):
 
 @pytest.mark.parametrize("B,T,V,beam,sharp,order", R.CASES)
 def test_empty_and_all_zero_graphs_are_the_searches_without_a_graph(tmp_path, B, T, V, beam, sharp, order):
-    """Bit for bit: with the LM arguments oe_ctc_prefix_beam_lm's lists, order, total, ctc and lm; without an LM and without a
-    length bonus oe_ctc_prefix_beam's lists and scores."""
+    """Bit for bit: with the LM arguments the LM-fused search's lists, order, total, ctc and lm; without an LM and without a
+    length bonus the plain search's lists and scores."""
     from openeat_amd import hip, ops
     logits, lens, path, t2c = R.make_case(tmp_path, B, T, V, beam, sharp, order)
     lm = NgramLM(path, t2c)
@@ -212,24 +212,34 @@ def test_bad_arguments_are_reported_not_launched(tmp_path):
     top_i = torch.zeros(B, T, 17, dtype=torch.int64, device=DEV)
     with pytest.raises(RuntimeError, match="beam must be 1..16"):
         hip.ctc_prefix_beam_ctx_device(top_p, top_i, None, 17, graph)
-    uni, table, tok2word = lm.device_tables(DEV)
-    edges, fail, out, pend = graph.device_tables(DEV)
     ws = torch.zeros(B * T * 4 * 2 + 1, dtype=torch.int32, device=DEV)
     pre = torch.zeros(B, 4, T, dtype=torch.int32, device=DEV)
     plen = torch.zeros(B, 4, dtype=torch.int32, device=DEV)
     sc = [torch.zeros(B, 4, dtype=torch.float64, device=DEV) for _ in range(4)]
+    capacity = hip.context_graph(graph, DEV).capacity
 
-    def call(order=2, lw=0.5, lb=0.0, edges_=edges, cap=graph.capacity, probe=graph.max_probe, n=graph.n_states, c=0.37, uni_=uni,
-             table_=table, bias_=sc[3]):
-        hip.call("oe_ctc_prefix_beam_ctx", top_p, top_i, B, T, None, 4, T, uni_, lm.n_words, table_, lm.capacity, lm.max_probe, order,
-                 lm.bos_word, lm.eos_word, lm.unk_word, tok2word, int(tok2word.shape[0]), lw, lb, 1, edges_, cap, probe, fail, out,
-                 pend, n, c, 1, ws, pre, plen, sc[0], sc[1], sc[2], bias_)
+    def call(model=(), ctx=(), lw=0.5, lb=0.0, bias_=sc[3]):
+        """model / ctx: the fields of the oe_ngram_model / the oe_context_graph that are spoiled; None: the search without one."""
+        def spoiled(struct, fields):
+            for k, v in dict(fields).items():
+                setattr(struct, k, v)
+            return struct
 
-    for kw, message in ((dict(order=6), "order must be 1..5"), (dict(table_=None), "null pointer"), (dict(edges_=None), "null pointer"),
-                        (dict(bias_=None), "null pointer"), (dict(lw=float("nan")), "finite"), (dict(lb=float("inf")), "finite"),
-                        (dict(uni_=None, lb=float("inf")), "finite"), (dict(c=float("nan")), "finite"), (dict(c=-1.0), ">= 0"),
-                        (dict(n=0), "n_states"), (dict(n=(1 << 20) + 1), "n_states"), (dict(cap=graph.capacity + 1), "power of two"),
-                        (dict(cap=0), "power of two"), (dict(probe=-1), "max_probe"), (dict(probe=graph.capacity), "max_probe")):
+        hip.prefix_beam(hip.prefix_beam_args(top_p, top_i, None, 4, T, ws, pre, plen, sc[0], sc[1], sc[2], bias_,
+                                             lm=None if model is None else spoiled(hip.ngram_model(lm, DEV), model),
+                                             ctx=None if ctx is None else spoiled(hip.context_graph(graph, DEV), ctx),
+                                             lm_weight=lw, length_bonus=lb, eos=True, final=True))
+
+    for kw, message in ((dict(model=dict(order=6)), "order must be 1..5"), (dict(model=dict(table=None)), "null pointer"),
+                        (dict(ctx=dict(edges=None)), "null pointer"), (dict(bias_=None), "null pointer"), (dict(lw=float("nan")), "finite"),
+                        (dict(lb=float("inf")), "finite"), (dict(model=None, lb=float("inf")), "finite"),
+                        (dict(ctx=dict(c=float("nan"))), "finite"), (dict(ctx=dict(c=-1.0)), ">= 0"), (dict(ctx=dict(n_states=0)), "n_states"),
+                        (dict(ctx=dict(n_states=(1 << 20) + 1)), "n_states"), (dict(ctx=dict(capacity=capacity + 1)), "power of two"),
+                        (dict(ctx=dict(capacity=0)), "power of two"), (dict(ctx=dict(max_probe=-1)), "max_probe"),
+                        (dict(ctx=dict(max_probe=capacity)), "max_probe"),
+                        # the plain search has no weights to ignore; a model / a graph alone, with a table missing
+                        (dict(model=None, ctx=None, lw=0.5, lb=0.0), "plain search"), (dict(model=None, ctx=None, lw=0.0, lb=0.5), "plain search"),
+                        (dict(ctx=None, model=dict(table=None)), "null pointer"), (dict(model=None, ctx=dict(fail=None)), "null pointer")):
         with pytest.raises(RuntimeError, match=message):
             call(**kw)
     torch.cuda.synchronize()

@@ -1,4 +1,4 @@
-"""GPU: CTC prefix beam search with n-gram LM shallow fusion on the device (oe_ctc_prefix_beam_lm) against the yardstick
+"""GPU: CTC prefix beam search with n-gram LM shallow fusion on the device (oe_ctc_prefix_beam with an LM) against the yardstick
 (tests/ctc_lm_beam_ref.py: the reference's dict loop with the fused key, RefLM for the LM terms - independent of the product
 and held to the host recursion and to RefLM.score by tests/test_ctc_lm_beam_ref.py), run on the device's own top-k.
 
@@ -161,20 +161,21 @@ def test_bad_arguments_are_reported_not_launched(tmp_path):
     top_i = torch.zeros(B, T, 17, dtype=torch.int64, device=DEV)
     with pytest.raises(RuntimeError, match="beam must be 1..16"):
         hip.ctc_prefix_beam_lm_device(top_p, top_i, None, 17, lm, 0.5)
-    uni, table, tok2word = lm.device_tables(DEV)
     ws = torch.zeros(B * T * 4 * 2 + 1, dtype=torch.int32, device=DEV)
     pre = torch.zeros(B, 4, T, dtype=torch.int32, device=DEV)
     plen = torch.zeros(B, 4, dtype=torch.int32, device=DEV)
     sc = [torch.zeros(B, 4, dtype=torch.float64, device=DEV) for _ in range(3)]
 
-    def call(table_, order):
-        hip.call("oe_ctc_prefix_beam_lm", top_p, top_i, B, T, None, 4, T, uni, lm.n_words, table_, lm.capacity, lm.max_probe, order,
-                 lm.bos_word, lm.eos_word, lm.unk_word, tok2word, int(tok2word.shape[0]), 0.5, 0.0, 1, ws, pre, plen, *sc)
+    def call(**model_fields):
+        model = hip.ngram_model(lm, DEV)
+        for k, v in model_fields.items():
+            setattr(model, k, v)
+        hip.prefix_beam(hip.prefix_beam_args(top_p, top_i, None, 4, T, ws, pre, plen, *sc, lm=model, lm_weight=0.5, length_bonus=0.0, eos=True))
 
     with pytest.raises(RuntimeError, match="order must be 1..5"):
-        call(table, 6)
+        call(order=6)
     with pytest.raises(RuntimeError, match="null pointer"):
-        call(None, 2)
+        call(table=None)
     torch.cuda.synchronize()
     assert int(plen.abs().sum()) == 0 and all(float(x.abs().sum()) == 0.0 for x in sc)      # nothing ran
 

@@ -55,15 +55,13 @@ def _hypotheses(ref, t2c, R, ld, rng):
 
 def _call(lm, tokens, klens, bos, eos):
     from openeat_amd import hip
-    uni, table, tok2word = lm.device_tables(DEV)
     R, ld = tokens.shape
     tk = torch.from_numpy(tokens).to(DEV)
     kl = torch.from_numpy(klens).to(DEV)
     score = torch.full((R,), 123.0, dtype=torch.float64, device=DEV)
     tok_logp = torch.full((R, ld + 1), FILL_LP, dtype=torch.float64, device=DEV)
     tok_order = torch.full((R, ld + 1), FILL_ORDER, dtype=torch.int32, device=DEV)
-    hip.call("oe_ngram_score", uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word,
-             tok2word, int(tok2word.shape[0]), tk, ld, kl, R, int(bos), int(eos), score, tok_logp, tok_order)
+    hip.call("oe_ngram_score", hip.ngram_model(lm, DEV), tk, ld, kl, R, int(bos), int(eos), score, tok_logp, tok_order)
     torch.cuda.synchronize()
     return score.cpu().numpy(), tok_logp.cpu().numpy(), tok_order.cpu().numpy()
 

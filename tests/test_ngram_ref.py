@@ -208,8 +208,9 @@ def test_surface_header_export_binding_alias():
     from openeat_amd.models.ngram_lm import NgramLM as Own
     assert NgramLM is Own and callable(ops.ngram_score)
     # arguments are checked before anything is launched
-    rc = hip.lib().oe_ngram_score(None, 1, None, 2, 0, 3, 0, 0, 0, None, 1, None, 0, None, 1, 1, 1, None, None, None, None)
-    assert rc != 0 and b"null" in hip.lib().oe_last_error()
+    for model in (None, hip.NgramModel(None, None, None, 2, 1, 0, 3, 0, 0, 0, 1)):         # no model; one whose pointers are NULL
+        rc = hip.lib().oe_ngram_score(model, None, 0, None, 1, 1, 1, None, None, None, None)
+        assert rc != 0 and b"null" in hip.lib().oe_last_error()
 
 
 def test_ngram_score_has_no_cpu_fallback(tiny):

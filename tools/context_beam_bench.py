@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The hotword-biased CTC prefix beam search (oe_ctc_prefix_beam_ctx) against the plain (oe_ctc_prefix_beam) and the LM-fused
-one (oe_ctc_prefix_beam_lm) on the same top-k: the four instantiations of beam.hip's kernel (GPU box).
+"""The hotword-biased CTC prefix beam search (oe_ctc_prefix_beam with a context graph) against the plain and the LM-fused one
+on the same top-k: the four instantiations of beam.hip's kernel (GPU box).
 
   python tools/context_beam_bench.py      # 64 utterances x 10 s (250 frames), beam 10; graphs of 0, 100 and 1000 phrases
 
@@ -47,29 +47,23 @@ def main():
     logits[:, :, 0] += 3.0
     top_p, top_i = ops.topk_rows(logits.to(DEV), BEAM, log_softmax=True)
     lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
-    ws = torch.zeros(hip.lib().oe_ctc_prefix_beam_ctx_workspace_bytes(B, T, BEAM) // 4, dtype=torch.int32, device=DEV)
+    ws = torch.zeros(hip.lib().oe_ctc_prefix_beam_workspace_bytes(B, T, BEAM) // 4, dtype=torch.int32, device=DEV)
     pre = torch.zeros(B, BEAM, T, dtype=torch.int32, device=DEV)
     plen = torch.zeros(B, BEAM, dtype=torch.int32, device=DEV)
     total, ctc, lms, bias = (torch.zeros(B, BEAM, dtype=torch.float64, device=DEV) for _ in range(4))
     lm = synthetic_lm(3)
-    uni, table, tok2word = lm.device_tables(DEV)
-    model = (uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word, lm.unk_word, tok2word, V)
-    no_model = (None, 0, None, 0, 0, 0, 0, 0, 0, None, 0)
+    model = hip.ngram_model(lm, DEV)
 
-    def plain():
-        hip.call("oe_ctc_prefix_beam", top_p, top_i, B, T, lens, BEAM, T, ws, pre, plen, ctc)
+    def search(*outs, **kw):
+        a = hip.prefix_beam_args(top_p, top_i, lens, BEAM, T, ws, pre, plen, *outs, **kw)
+        return lambda: hip.prefix_beam(a)
 
-    def fused():
-        hip.call("oe_ctc_prefix_beam_lm", top_p, top_i, B, T, lens, BEAM, T, *model, 0.5, 0.0, 1, ws, pre, plen, total, ctc, lms)
+    plain = search(ctc)
+    fused = search(total, ctc, lms, lm=model, lm_weight=0.5)
 
     def biased(graph, with_lm):
-        edges, fail, out, pend = graph.device_tables(DEV)
-
-        def run():
-            hip.call("oe_ctc_prefix_beam_ctx", top_p, top_i, B, T, lens, BEAM, T, *(model if with_lm else no_model), 0.5, 0.0, 1, edges,
-                     graph.capacity, graph.max_probe, fail, out, pend, graph.n_states, float(graph.context_score), 1, ws, pre, plen,
-                     total, ctc, lms if with_lm else None, bias)
-        return run
+        return search(total, ctc, lms if with_lm else None, bias, lm=model if with_lm else None, ctx=hip.context_graph(graph, DEV),
+                      lm_weight=0.5)
 
     plain()
     torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The LM-fused CTC prefix beam search (oe_ctc_prefix_beam_lm) against the plain one (oe_ctc_prefix_beam) on the same top-k:
+"""The LM-fused CTC prefix beam search (oe_ctc_prefix_beam with an n-gram model) against the plain one on the same top-k:
 the two instantiations of beam.hip's kernel (GPU box).
 
   python tools/lm_beam_bench.py           # 64 utterances x 250 frames, beam 10, synthetic n-gram models of order 3 and 5
@@ -62,25 +62,27 @@ def main():
     logits[:, :, 0] += 3.0
     top_p, top_i = ops.topk_rows(logits.to(DEV), BEAM, log_softmax=True)
     lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
-    ws = torch.zeros(hip.lib().oe_ctc_prefix_beam_lm_workspace_bytes(B, T, BEAM) // 4, dtype=torch.int32, device=DEV)
+    ws = torch.zeros(hip.lib().oe_ctc_prefix_beam_workspace_bytes(B, T, BEAM) // 4, dtype=torch.int32, device=DEV)
     pre = torch.zeros(B, BEAM, T, dtype=torch.int32, device=DEV)
     plen = torch.zeros(B, BEAM, dtype=torch.int32, device=DEV)
     total, ctc, lms = (torch.zeros(B, BEAM, dtype=torch.float64, device=DEV) for _ in range(3))
 
+    plain_args = hip.prefix_beam_args(top_p, top_i, lens, BEAM, T, ws, pre, plen, ctc)
+
     def plain():
-        hip.call("oe_ctc_prefix_beam", top_p, top_i, B, T, lens, BEAM, T, ws, pre, plen, ctc)
+        hip.prefix_beam(plain_args)
 
     plain()
     print(f"top-k: {B} utterances x {T} frames, beam {BEAM}, V {V}; mean 1-best length {float(plen[:, 0].float().mean()):.1f} tokens")
     for order in (3, 5):
         lm = synthetic_lm(order)
-        uni, table, tok2word = lm.device_tables(DEV)
+        fused_args = hip.prefix_beam_args(top_p, top_i, lens, BEAM, T, ws, pre, plen, total, ctc, lms, lm=hip.ngram_model(lm, DEV),
+                                          lm_weight=0.5, length_bonus=0.0, eos=True)
         print(f"model: order {lm.order}, {lm.n_ngrams} n-grams, table {lm.capacity} slots = {lm.capacity * 16 / 2 ** 20:.0f} MiB, "
               f"longest displacement {lm.max_probe}")
 
-        def fused(w=0.5):
-            hip.call("oe_ctc_prefix_beam_lm", top_p, top_i, B, T, lens, BEAM, T, uni, lm.n_words, table, lm.capacity, lm.max_probe,
-                     lm.order, lm.bos_word, lm.eos_word, lm.unk_word, tok2word, V, w, 0.0, 1, ws, pre, plen, total, ctc, lms)
+        def fused():
+            hip.prefix_beam(fused_args)
 
         fused()
         torch.cuda.synchronize()

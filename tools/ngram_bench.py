@@ -71,14 +71,13 @@ def kernel_part():
         walk = g3[rng.integers(0, len(g3), (R, ld // 6 + 1))].reshape(R, -1)[:, : ld // 2] - 3      # word id -> token id (may be < 0: <unk>)
         tokens[:, : walk.shape[1]] = np.clip(walk, 0, V - 1)
         tk, ln = torch.from_numpy(tokens).to(DEV), torch.from_numpy(lens).to(DEV)
-        uni, table, tok2word = lm.device_tables(DEV)
+        model = hip.ngram_model(lm, DEV)
         score = torch.empty(R, dtype=torch.float64, device=DEV)
         order = torch.zeros(R, ld + 1, dtype=torch.int32, device=DEV)
         lp = torch.zeros(R, ld + 1, dtype=torch.float64, device=DEV)
 
         def call(per_token=False):
-            hip.call("oe_ngram_score", uni, lm.n_words, table, lm.capacity, lm.max_probe, lm.order, lm.bos_word, lm.eos_word,
-                     lm.unk_word, tok2word, V, tk, ld, ln, R, 1, 1, score, lp if per_token else None, order if per_token else None)
+            hip.call("oe_ngram_score", model, tk, ld, ln, R, 1, 1, score, lp if per_token else None, order if per_token else None)
 
         call(True)
         hist = torch.bincount(order[order > 0].flatten(), minlength=4).tolist()[1:]
