@@ -699,6 +699,26 @@ typedef struct oe_ngram_model {
 int oe_ngram_score(const oe_ngram_model* model, const int* tokens, long ld, const int* lens, int R, int bos, int eos,
                    double* score, double* tok_logp, int* tok_order, void* stream);
 
+/* The n-gram LM term of C candidate next tokens of each of R growing hypotheses: the conditional log10 p(w | hypothesis) a
+ * search step mixes into its pruning key, where oe_ngram_score scores finished sequences.
+ * Rows: row r is the hypothesis tokens[r, :lens[r]] (tokens (R, ld) i32, the tokens after <sos>; lens (R) i32);
+ * lens[r] < 0 = the slot does not exist, lens[r] above ld is clamped to ld; what lies behind the length is never read.
+ * Candidates: cand (R, C) i32, out[r, j] is for token cand[r, j];  cand == NULL = every token: C must equal model->V and
+ * out[r, j] is for token j.  eos_tok: the token id whose word is </s> (-1: no token is).
+ * The value: out[r, j] is the term oe_ngram_score would write to tok_logp[r, len] had the candidate been appended to the
+ * hypothesis with bos = 1 - for the eos_tok candidate its </s> term, with eos = 1.  The same ARPA back-off definition: every
+ * other token maps to its word as in oe_ngram_score (the blank, ids outside 0..V-1 and unmapped tokens count as <unk> and
+ * get a finite value), the context is the last order-1 words of <s> + hypothesis, the back-offs of the longer listed
+ * contexts are added in float64, longest first, the log10 p last - so the result is bit-identical to oe_ngram_score's
+ * tok_logp and to NgramLM.full_scores on the host.  A missing slot: all C entries of its row are -inf.
+ * out (R, C) f64.  An entry is the same bits whether its token is reached through cand or through the full-vocabulary
+ * form, and for any grid shape.
+ * Refused before any launch (oe_last_error): a null pointer other than cand, C < 1, cand == NULL with C != V, eos_tok
+ * outside -1..V-1, ld < 0, and what every oe_ngram_model entry point refuses.
+ * One launch, no workspace, no atomics, no allocation, no host read: capturable. */
+int oe_ngram_next(const oe_ngram_model* model, const int* tokens, long ld, const int* lens, int R, const int* cand, int C,
+                  int eos_tok, double* out, void* stream);
+
 /* A context graph (the hotwords of the biased search below) as the kernel reads it - an Aho-Corasick automaton built by
  * openeat_amd/utils/context_graph.py, which states the layout once more.  States are trie nodes, the root is 0,
  * n_states <= 2^20:

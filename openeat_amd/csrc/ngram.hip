@@ -140,3 +140,128 @@ extern "C" int oe_ngram_score(const oe_ngram_model* model, const int* tokens, lo
     OE_LAUNCH_CHECK("ngram_score");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The LM term of every candidate next token of every hypothesis (oe_ngram_next; semantics in include/openeat_hip.h): what a
+// search step needs, where ngram_score_kernel scores finished sequences.  One block = one wave = one hypothesis x one slice
+// of NGN_SLICE candidates; grid (R, slices).
+//
+// The context is the last n = min(order-1, len+1) words of <s> + hypothesis.  Its suffixes of 1..n words are the only
+// dependent probes: lane j-1 walks the suffix of j words (j-1 probes, each entry found from the one before) and leaves
+// (is it listed, its entry number, its back-off) in LDS - once per block, at most order-2 probes deep.  Then every lane
+// owns NGN_PER candidates: from the longest listed suffix down, one lookup of (suffix's entry, word) per level until the
+// n-gram is listed, the back-off of the level added where it is not; then the unigram.  A suffix that is not listed adds
+// nothing and is not probed (its extensions cannot be listed).  The first slot of a level is read for all of a lane's
+// candidates before any is compared, and the unigrams before the levels: the loads of a lane do not wait for one another.
+// A term is a float64 sum in the order of ngram_score_kernel (back-offs longest first, then the log10 p) of the same float32
+// values, so it is the same bits, for any candidate order and any grid shape.
+//
+// Bound: latency / gather.  R x C x (listed levels) independent 16-byte reads into a table far larger than LDS.
+#define NGN_PER 4
+#define NGN_SLICE (OE_WAVE * NGN_PER)
+
+__global__ __launch_bounds__(OE_WAVE) void ngram_next_kernel(NgModel m, const int* __restrict__ tokens, long ld,
+                                                             const int* __restrict__ lens, const int* __restrict__ cand, int C,
+                                                             int eos_tok, double* __restrict__ out) {
+    __shared__ int wd[NG_MAXORDER];                              // the context's words, oldest first
+    __shared__ int listed[NG_MAXORDER];                          // [j]: the suffix of j words, j = 1 .. n
+    __shared__ unsigned ent[NG_MAXORDER];
+    __shared__ float bo[NG_MAXORDER];
+
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const long j0 = (long)blockIdx.y * NGN_SLICE + lane;         // this lane's candidates: j0 + u * 64
+    double* o = out + (long)r * C;
+    const int len_raw = lens[r];
+    if (len_raw < 0) {                                           // the slot does not exist (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < NGN_PER; ++u)
+            if (j0 + u * OE_WAVE < C) o[j0 + u * OE_WAVE] = -__builtin_huge_val();
+        return;
+    }
+    const int len = (int)min((long)len_raw, ld);
+    const int P = len + 1;                                       // <s> and the tokens
+    const int n = min(m.order - 1, P);
+    if (lane < n) {
+        const int q = P - n + lane;
+        wd[lane] = q == 0 ? m.bos_word : ng_word(m, tokens[(long)r * ld + (q - 1)]);
+    }
+    __syncthreads();
+    if (lane < n) {                                              // the suffix of j = lane + 1 words: wd[n-j .. n-1]
+        const int j = lane + 1;
+        long e = wd[n - j];
+        float a = 0.f, b = m.unigrams[e].y;
+        int ok = 1;
+        for (int k = 1; k < j; ++k) {
+            const unsigned long long key = ((unsigned long long)e << 32) | (unsigned)wd[n - j + k];
+            const long slot = ng_find(m.table, m.mask, m.max_probe, key, a, b);
+            if (slot < 0) { ok = 0; break; }
+            e = (long)m.n_words + slot;
+        }
+        listed[j] = ok; ent[j] = (unsigned)e; bo[j] = b;
+    }
+    __syncthreads();
+
+    unsigned w[NGN_PER];
+    float uni[NGN_PER];
+    double term[NGN_PER];
+    bool open[NGN_PER];                                          // a candidate whose n-gram is not found yet
+#pragma unroll
+    for (int u = 0; u < NGN_PER; ++u) {
+        const long j = j0 + u * OE_WAVE;
+        open[u] = j < C;
+        term[u] = 0.0;
+        w[u] = 0; uni[u] = 0.f;
+        if (open[u]) {
+            const int tok = cand ? cand[(long)r * C + j] : (int)j;
+            w[u] = (unsigned)((eos_tok >= 0 && tok == eos_tok) ? m.eos_word : ng_word(m, tok));
+            uni[u] = m.unigrams[w[u]].x;
+        }
+    }
+    for (int j = n; j >= 1; --j) {
+        if (!listed[j]) continue;                                // wave-uniform
+        const unsigned long long hi = (unsigned long long)ent[j] << 32;
+        const double b = (double)bo[j];
+        unsigned long long slot[NGN_PER];
+        uint4 v[NGN_PER];
+#pragma unroll
+        for (int u = 0; u < NGN_PER; ++u) {
+            slot[u] = ng_mix(hi | w[u]) & m.mask;
+            if (open[u]) v[u] = m.table[slot[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < NGN_PER; ++u) {
+            if (!open[u]) continue;
+            const unsigned long long key = hi | w[u];
+            for (int d = 0;; ++d) {                              // ng_find's walk: the key, an empty slot, or max_probe + 1 slots
+                const unsigned long long k = ((unsigned long long)v[u].y << 32) | v[u].x;
+                if (k == key) { term[u] += (double)__uint_as_float(v[u].z); open[u] = false; break; }
+                if (k == NG_EMPTY || d == m.max_probe) { term[u] += b; break; }
+                slot[u] = (slot[u] + 1) & m.mask;
+                v[u] = m.table[slot[u]];
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NGN_PER; ++u) {
+        const long j = j0 + u * OE_WAVE;
+        if (j < C) o[j] = open[u] ? term[u] + (double)uni[u] : term[u];
+    }
+}
+
+extern "C" int oe_ngram_next(const oe_ngram_model* model, const int* tokens, long ld, const int* lens, int R, const int* cand, int C,
+                             int eos_tok, double* out, void* stream) {
+    OE_REQUIRE(model && model->unigrams && model->table && model->tok2word && tokens && lens && out, "oe_ngram_next: null pointer");
+    NgModel m;
+    if (ng_model_args("oe_ngram_next", model, &m)) return -1;
+    OE_REQUIRE(R >= 0 && m.V > 0 && ld >= 0, "oe_ngram_next: bad shape R=%d V=%d ld=%ld", R, m.V, ld);
+    OE_REQUIRE(C >= 1, "oe_ngram_next: C must be >= 1 (got %d)", C);
+    OE_REQUIRE(cand || C == m.V, "oe_ngram_next: without cand every token is scored: C must equal V = %d (got %d)", m.V, C);
+    OE_REQUIRE(eos_tok >= -1 && eos_tok < m.V, "oe_ngram_next: eos_tok %d outside -1..%d", eos_tok, m.V - 1);
+    if (R == 0) return 0;
+    const int slices = (int)(((long)C + NGN_SLICE - 1) / NGN_SLICE);
+    OE_REQUIRE(slices <= 65535, "oe_ngram_next: C = %d needs more than 65535 slices of %d candidates", C, NGN_SLICE);
+    hipLaunchKernelGGL(ngram_next_kernel, dim3(R, slices), dim3(OE_WAVE), 0, (hipStream_t)stream, m, tokens, ld, lens, cand, C, eos_tok,
+                       out);
+    OE_LAUNCH_CHECK("ngram_next");
+    return 0;
+}

@@ -1,5 +1,6 @@
 // The n-gram model's arguments, the table's slot and its exact-key lookup, shared by the kernels that read an NgramLM on the
-// device (ngram.hip: scores of finished hypotheses; beam.hip: the LM state of every prefix inside the fused beam search).
+// device (ngram.hip: scores of finished hypotheses and the terms of candidate next tokens; beam.hip: the LM state of every
+// prefix inside the fused beam search).
 // Layout and key chaining: include/openeat_hip.h (oe_ngram_score) and openeat_amd/models/ngram_lm.py.
 #pragma once
 #include "oe_common.h"

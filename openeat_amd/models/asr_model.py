@@ -663,7 +663,8 @@ class ASRModel(torch.nn.Module):
     @torch.no_grad()
     def ctc_attention_beam_search(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int = 10,
                                   ctc_weight: float = 0.3, length_bonus: float = 0.0, ctc_candidates: Optional[int] = None,
-                                  max_len: Optional[int] = None, nbest: bool = False):
+                                  max_len: Optional[int] = None, nbest: bool = False, lm=None, lm_weight: float = 0.0,
+                                  lm_prebeam: bool = True):
         """Joint CTC/attention one-pass beam search (not in the reference; semantics in utils/joint_search.py and, for the CTC
         prefix score, include/openeat_hip.h): the decoder proposes `ctc_candidates` tokens per hypothesis (default
         min(2 beam_size, V, 64)), and each is ranked by (1 - ctc_weight) * attention + ctc_weight * CTC prefix score +
@@ -672,7 +673,11 @@ class ASRModel(torch.nn.Module):
         Unlike recognize, which reproduces the reference's un-reordered decoder cache on purpose, this search reorders the
         per-layer decoder cache by the surviving parents after every pruning.  max_len: the step limit (default: the batch's
         encoder length, as in recognize).  -> per utterance the best hypothesis' tokens without <eos>; nbest: per utterance
-        [(tokens, total, att, ctc)], finished hypotheses first, each group by total (ctc is 0 with ctc_weight == 0)."""
+        [(tokens, total, att, ctc)], finished hypotheses first, each group by total (ctc is 0 with ctc_weight == 0).
+        lm (an NgramLM over this model's vocab_size tokens), lm_weight, lm_prebeam: n-gram LM fusion inside the search - the
+        total gains lm_weight * the hypothesis' LM score (log10, </s> included once it is finished), one oe_ngram_next launch
+        per step; lm_prebeam: the LM also takes part in choosing the candidates (utils/joint_search.py).  With an LM the
+        nbest entries are (tokens, total, att, ctc, lm)."""
         from openeat_amd.utils.joint_search import joint_beam_search
         if not 0.0 <= ctc_weight <= 1.0:
             raise ValueError(f"ctc_weight must lie in [0, 1] (got {ctc_weight})")
@@ -683,6 +688,13 @@ class ASRModel(torch.nn.Module):
             raise ValueError(f"ctc_candidates must lie in 1..{min(64, self.vocab_size)} (got {C})")
         if beam_size < 1:
             raise ValueError(f"beam_size must be >= 1 (got {beam_size})")
+        if lm is not None:
+            if not isinstance(lm, NgramLM):
+                raise ValueError(f"lm must be an NgramLM (got {type(lm).__name__})")
+            if not math.isfinite(lm_weight):
+                raise ValueError(f"lm_weight must be finite (got {lm_weight})")
+            if len(lm.tok2word) != self.vocab_size:
+                raise ValueError(f"the LM maps {len(lm.tok2word)} tokens, the model has {self.vocab_size}")
         assert features.shape[0] == features_length.shape[0]
         device = features.device
         encoder_out, encoder_mask, _ = self._encode(features, features_length)
@@ -703,7 +715,11 @@ class ASRModel(torch.nn.Module):
             p, cache, _ = self.decoder.forward_one_step(hyps, hyps_mask, memory, memory_mask, cache=cache)
             return ops.log_softmax_rows(p)
 
-        res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len)
+        if lm is None:
+            res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len)
+        else:
+            res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len, 0, lm,
+                                    float(lm_weight), lm_prebeam)
         if nbest:
-            return [[(t, total, att, ctc) for t, total, att, ctc, _ in nb] for nb in res]
+            return [[h[:4] + h[5:] for h in nb] for nb in res]
         return [nb[0][0] if nb else [] for nb in res]

@@ -2385,6 +2385,38 @@ def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token:
     return (score, tok_logp, tok_order) if per_token else score
 
 
+def ngram_next(lm, tokens, lens, cand=None, eos=None):
+    """The n-gram LM term of candidate next tokens of R growing hypotheses (oe_ngram_next; semantics in
+    include/openeat_hip.h): `lm` an openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids (after <sos>) and
+    lens (R) on the device (a negative length: the slot does not exist, its row is -inf; what lies behind a length is not
+    read), cand (R, C) integer token ids or None = every token of the LM's V, eos the token id whose word is </s> (None: no
+    token is) -> (R, C) or (R, V) float64 log10 p(candidate | hypothesis), the bits of ngram_score's tok_logp.
+    No host read, no allocation beyond the output: capturable."""
+    ts = (tokens, lens) if cand is None else (tokens, lens, cand)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError("ngram_next: openeat_amd ops need CUDA tensors; there is no CPU fallback (on the host: NgramLM.full_scores)")
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ts) or tokens.dim() != 2 or lens.shape != tokens.shape[:1] \
+            or (cand is not None and (cand.dim() != 2 or cand.shape[0] != tokens.shape[0])):
+        raise TypeError("ngram_next: tokens (R, ld), lens (R) and cand (R, C) must be integer tensors")
+    dev = tokens.device
+    R, ld = int(tokens.shape[0]), int(tokens.shape[1])
+    V = int(lm.tok2word.shape[0])
+    C = V if cand is None else int(cand.shape[1])
+    if C < 1:
+        raise ValueError("ngram_next: cand (R, C) needs at least one candidate per hypothesis")
+    eos = -1 if eos is None else int(eos)
+    if not -1 <= eos < V:
+        raise ValueError(f"ngram_next: eos {eos} is outside the LM's 0..{V - 1}")
+    # a zero-width matrix has no storage to point at: nothing of the stand-in is read
+    tok32 = tokens.to(torch.int32).contiguous() if ld else torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
+    out = torch.empty(R, C, dtype=torch.float64, device=dev)
+    if R == 0:
+        return out
+    hip.call("oe_ngram_next", hip.ngram_model(lm, dev), tok32, ld, lens.to(torch.int32).contiguous(), R,
+             None if cand is None else cand.to(torch.int32).contiguous(), C, eos, out)
+    return out
+
+
 def edit_distance(ref, ref_lens, hyp, hyp_lens, group: int = 1, align: bool = False):
     """Edit distance of P (reference, hypothesis) pairs on the device (oe_edit_distance; semantics and tie order in
     include/openeat_hip.h): ref (P / group, Nmax) and hyp (P, Mmax) integer token ids, ref_lens (P / group) and hyp_lens (P)

@@ -21,7 +21,25 @@ it extends (None at the first step) - what a scorer with a per-row cache reorder
 
 The bookkeeping is torch tensor plumbing of fixed shape; one step (score + prune) reads nothing on the host and is capturable.
 The totals are float64, which oe_topk_rows (float32) does not take: the prune is a stable descending torch.sort, the same
-(slot, rank) tie order.  The loop reads one flag per step on the host, the all-finished test, as ASRModel.recognize does."""
+(slot, rank) tie order.  The loop reads one flag per step on the host, the all-finished test, as ASRModel.recognize does.
+
+With an n-gram LM (`lm`, an openeat_amd.models.ngram_lm.NgramLM, and `lm_weight`; Hori et al. 2017's three-way sum) a hypothesis
+also carries m, the float64 left-to-right sum of its tokens' LM terms log10 p(token | <s> + the tokens before it) - for <eos>
+the </s> term, so m includes it once the hypothesis is finished.  The terms are oe_ngram_next's (include/openeat_hip.h), in
+log10 units, mixed in unconverted as in the fused prefix beam and in the rescoring.  Candidate c has m' = m + term(c) and
+    total = (((1 - lam) a' + lam k') + beta len) + lm_weight m',
+products and sums each rounded on their own, in this order (with lam == 0 the CTC term is left out, as above); a finished
+hypothesis carries m unchanged, as it does a and k.  Which C tokens are candidates depends on `lm_prebeam`:
+  True:  one full-vocabulary oe_ngram_next per step gives L (R, V), and the candidates are the top-C tokens, in oe_topk_rows
+         order, of the float32 key (l(. | g) in float64 + lm_weight * L) - the LM takes part in the pre-selection; the decoder
+         weight deliberately does not enter this key, so with lm_weight == 0 it is l(. | g) to the bit for every ctc_weight,
+         1.0 included.  l(c) and term(c) are then gathered from l and L: the exact values, not the key's.
+  False: the candidates are the decoder's own top-C, exactly as without an LM, and one candidate-form oe_ngram_next scores
+         just those.
+With an LM and lm_weight == 0 the n-best lists, their order and the bits of total, att and ctc are those of the search without
+an LM, in both modes.  The step stays free of host reads and capturable.  With lm None nothing changes: no code path, no bit,
+no launch.  The result rows gain a sixth element, m."""
+import math
 from typing import Callable, List, NamedTuple, Optional
 
 import torch
@@ -38,10 +56,19 @@ class BeamState(NamedTuple):
     finished: torch.Tensor    # (R) bool
     length: torch.Tensor      # (R) int64 non-<eos> tokens
     state: Optional[torch.Tensor]     # (R, Tmax, 2) float64 CTC prefix states (None with ctc_weight == 0)
+    lm: Optional[torch.Tensor] = None  # (R) float64 sum of the LM terms (None without an LM)
 
 
-def initial_state(logp: torch.Tensor, lens: Optional[torch.Tensor], beam: int, ctc_weight: float, blank: int = 0) -> BeamState:
-    """The one empty hypothesis per utterance in slot 0; the other slots do not exist yet."""
+def _check_lm(lm, lm_weight):
+    from openeat_amd.models.ngram_lm import NgramLM
+    if not isinstance(lm, NgramLM):
+        raise ValueError(f"lm must be an openeat_amd.models.ngram_lm.NgramLM (got {type(lm).__name__})")
+    if not math.isfinite(lm_weight):
+        raise ValueError(f"lm_weight must be finite (got {lm_weight})")
+
+
+def initial_state(logp: torch.Tensor, lens: Optional[torch.Tensor], beam: int, ctc_weight: float, blank: int = 0, lm=None) -> BeamState:
+    """The one empty hypothesis per utterance in slot 0; the other slots do not exist yet.  lm: the search's LM or None."""
     B, dev = logp.shape[0], logp.device
     R = B * beam
     total = torch.full((B, beam), -float("inf"), dtype=torch.float64, device=dev)
@@ -49,12 +76,15 @@ def initial_state(logp: torch.Tensor, lens: Optional[torch.Tensor], beam: int, c
     zeros = torch.zeros(R, dtype=torch.float64, device=dev)
     state = ops.ctc_prefix_score_init(logp, lens, group=beam, blank=blank) if ctc_weight > 0 else None
     return BeamState(torch.zeros(R, 0, dtype=torch.int64, device=dev), None, zeros, zeros.clone(), total.view(R),
-                     torch.zeros(R, dtype=torch.bool, device=dev), torch.zeros(R, dtype=torch.int64, device=dev), state)
+                     torch.zeros(R, dtype=torch.bool, device=dev), torch.zeros(R, dtype=torch.int64, device=dev), state,
+                     None if lm is None else zeros.clone())
 
 
 def search_step(logp: torch.Tensor, lens: Optional[torch.Tensor], st: BeamState, att_logp: torch.Tensor, beam: int, C: int, eos: int,
-                ctc_weight: float, length_bonus: float, blank: int = 0, cand_state: Optional[torch.Tensor] = None) -> BeamState:
-    """One step: candidates, their CTC prefix scores, the prune.  att_logp (R, V) float32 for st's rows.  No host read."""
+                ctc_weight: float, length_bonus: float, blank: int = 0, cand_state: Optional[torch.Tensor] = None, lm=None,
+                lm_weight: float = 0.0, lm_prebeam: bool = True) -> BeamState:
+    """One step: candidates, their CTC prefix scores (and LM terms, with `lm`: st from initial_state(..., lm=lm)), the prune.
+    att_logp (R, V) float32 for st's rows.  No host read."""
     dev = logp.device
     R = st.total.shape[0]
     B = R // beam
@@ -62,7 +92,23 @@ def search_step(logp: torch.Tensor, lens: Optional[torch.Tensor], st: BeamState,
     ninf = -float("inf")
     alive = st.total > ninf
     live = alive & ~st.finished
-    top_lp, top_i = ops.topk_rows(att_logp, C)                              # (R, C): descending, ties to the lowest id
+    if lm is None:
+        top_lp, top_i = ops.topk_rows(att_logp, C)                          # (R, C): descending, ties to the lowest id
+    else:
+        _check_lm(lm, lm_weight)
+        lmw = float(lm_weight)
+        # every row is scored on all its columns: the terms of finished and missing rows are finite and masked below
+        lm_len = torch.full((R,), st.tokens.shape[1], dtype=torch.int32, device=dev)
+        if lm_prebeam:
+            if lm.tok2word.shape[0] != att_logp.shape[1]:
+                raise ValueError(f"the LM maps {lm.tok2word.shape[0]} tokens, the scorer gives {att_logp.shape[1]}")
+            L = ops.ngram_next(lm, st.tokens, lm_len, None, eos)            # (R, V)
+            _, top_i = ops.topk_rows((att_logp.double() + lmw * L).float(), C)
+            top_lp, term = att_logp.gather(1, top_i), L.gather(1, top_i)
+        else:
+            top_lp, top_i = ops.topk_rows(att_logp, C)
+            term = ops.ngram_next(lm, st.tokens, lm_len, top_i, eos)
+        lmv = st.lm.unsqueeze(1) + term
     is_eos = top_i == eos
     att = st.att.unsqueeze(1) + top_lp.double()
     length = st.length.unsqueeze(1) + (~is_eos).long()
@@ -74,6 +120,8 @@ def search_step(logp: torch.Tensor, lens: Optional[torch.Tensor], st: BeamState,
         last = st.tokens[:, -1] if st.tokens.shape[1] else torch.zeros(R, dtype=torch.int64, device=dev)
         ctc, new_states = ops.ctc_prefix_score(logp, lens, st.state, hyp_len, last, top_i, eos, group=beam, blank=blank, cand_state=cand_state)
         total = (1.0 - lam) * att + lam * ctc + beta * length.double()
+    if lm is not None:
+        total = total + lmw * lmv
     total = total.masked_fill(~live.unsqueeze(1), ninf)
     # a finished hypothesis yields itself once, at its slot's first rank; the token appended behind its <eos> is <eos>
     fin = st.finished.unsqueeze(1)
@@ -81,6 +129,8 @@ def search_step(logp: torch.Tensor, lens: Optional[torch.Tensor], st: BeamState,
     total = torch.where(keep, st.total.unsqueeze(1), total)
     att = torch.where(fin, st.att.unsqueeze(1), att)
     ctc = torch.where(fin, st.ctc.unsqueeze(1), ctc)
+    if lm is not None:
+        lmv = torch.where(fin, st.lm.unsqueeze(1), lmv)
     length = torch.where(fin, st.length.unsqueeze(1), length)
     tok = torch.where(fin, torch.full_like(top_i, eos), top_i)
     # prune: stable, so ties stay in (slot, rank) order; -inf (dropped candidates, missing slots) sorts last
@@ -92,33 +142,41 @@ def search_step(logp: torch.Tensor, lens: Optional[torch.Tensor], st: BeamState,
     tokens = torch.cat((st.tokens.index_select(0, parents), new_tok.unsqueeze(1)), dim=1)
     state = new_states[parents, :, rank] if lam > 0 else None              # (R, Tmax, 2); unread for finished and missing rows
     return BeamState(tokens, parents, att.reshape(-1).index_select(0, flat), ctc.reshape(-1).index_select(0, flat), best,
-                     (new_tok == eos) & (best > ninf), length.reshape(-1).index_select(0, flat), state)
+                     (new_tok == eos) & (best > ninf), length.reshape(-1).index_select(0, flat), state,
+                     None if lm is None else lmv.reshape(-1).index_select(0, flat))
 
 
 def joint_beam_search(logp: torch.Tensor, lens: Optional[torch.Tensor], step_fn: Callable, beam: int, C: int, eos: int,
-                      ctc_weight: float = 0.3, length_bonus: float = 0.0, max_steps: Optional[int] = None, blank: int = 0) -> List[list]:
+                      ctc_weight: float = 0.3, length_bonus: float = 0.0, max_steps: Optional[int] = None, blank: int = 0, lm=None,
+                      lm_weight: float = 0.0, lm_prebeam: bool = True) -> List[list]:
     """The batched search.  logp (B, Tmax, V) float32 CTC log-probabilities and lens (B) valid frames (or None) on the device;
     step_fn as in the module docstring; 1 <= C <= 64; max_steps defaults to Tmax.
-    -> per utterance [(tokens without <eos>, total, att, ctc, finished)], finished hypotheses first, each group by total."""
+    lm / lm_weight / lm_prebeam: n-gram LM fusion as in the module docstring (None: none).
+    -> per utterance [(tokens without <eos>, total, att, ctc, finished)], finished hypotheses first, each group by total; with
+    an LM the rows are (tokens, total, att, ctc, finished, lm)."""
     if not 0.0 <= ctc_weight <= 1.0:
         raise ValueError(f"ctc_weight must lie in [0, 1] (got {ctc_weight})")
     if not 1 <= C <= 64:
         raise ValueError(f"the joint search takes 1..64 candidates per hypothesis (got {C})")
     if beam < 1:
         raise ValueError(f"beam must be >= 1 (got {beam})")
+    if lm is not None:
+        _check_lm(lm, lm_weight)
     B, Tmax, _ = logp.shape
     max_steps = Tmax if max_steps is None else int(max_steps)
-    st = initial_state(logp, lens, beam, ctc_weight, blank)
+    st = initial_state(logp, lens, beam, ctc_weight, blank, lm)
     cand_state = torch.empty(B * beam, Tmax, C, 2, dtype=torch.float64, device=logp.device) if ctc_weight > 0 else None
     for step in range(max_steps):
         if step and bool(((st.total == -float("inf")) | st.finished).all()):   # the one host read of a step
             break
-        st = search_step(logp, lens, st, step_fn(st.tokens, st.parents), beam, C, eos, ctc_weight, length_bonus, blank, cand_state)
+        st = search_step(logp, lens, st, step_fn(st.tokens, st.parents), beam, C, eos, ctc_weight, length_bonus, blank, cand_state,
+                         lm, lm_weight, lm_prebeam)
     tokens, total, att, ctc = st.tokens.cpu(), st.total.cpu().tolist(), st.att.cpu().tolist(), st.ctc.cpu().tolist()
     fin, length = st.finished.cpu().tolist(), st.length.cpu().tolist()
+    lms = None if lm is None else st.lm.cpu().tolist()
     out = []
     for b in range(B):
         rows = [r for r in range(b * beam, (b + 1) * beam) if total[r] > -float("inf")]
         rows = [r for r in rows if fin[r]] + [r for r in rows if not fin[r]]
-        out.append([(tokens[r, : length[r]].tolist(), total[r], att[r], ctc[r], fin[r]) for r in rows])
+        out.append([(tokens[r, : length[r]].tolist(), total[r], att[r], ctc[r], fin[r]) + (() if lm is None else (lms[r],)) for r in rows])
     return out

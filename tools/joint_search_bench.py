@@ -2,7 +2,8 @@
 """The joint CTC/attention beam search at the decode leg's shape (GPU box): the CTC prefix-score kernel per step, the whole
 search, and recognize at the same beam on the same batch.
 
-  python tools/joint_search_bench.py      # 64 utterances x 10 s (249 encoder frames), beam 10, 20 candidates, V 3246
+  python tools/joint_search_bench.py                # 64 utterances x 10 s (249 encoder frames), beam 10, 20 candidates, V 3246
+  python tools/joint_search_bench.py --lm-order 3   # also (iii) and the search with an n-gram LM of that order (0 = off)
 
 (i)  oe_ctc_prefix_score alone, 640 hypotheses x 20 candidates x 249 frames, on hypotheses three tokens deep (their states come
      from the kernel itself), with and without the candidates' states.  The CTC log-probabilities are the log-softmax of random
@@ -11,7 +12,13 @@ search, and recognize at the same beam on the same batch.
 (ii) ASRModel.ctc_attention_beam_search (ctc_weight 0.3, and 0: the same loop without the kernel) and ASRModel.recognize on
      bench.py's 12-layer Conformer with seeded random weights, random features, every call to its end on the host clock between
      two device synchronisations; one warm-up round, then three alternating rounds, the middle one reported.  An untrained
-     decoder hardly ever emits <eos>, so all three run to the step limit, the encoder length: the same number of decoder steps."""
+     decoder hardly ever emits <eos>, so all three run to the step limit, the encoder length: the same number of decoder steps.
+(iii) --lm-order N: oe_ngram_next alone on 640 hypotheses twelve tokens deep - the full-vocabulary form (640 x 3246 terms) and
+     the candidate form (640 x 20, the top-20 of random attention scores) - timed as (i), and in (ii) the search at ctc_weight 0.3
+     with the LM at lm_weight 0.5, pre-selected with the LM (one full-vocabulary call per step) and without (one candidate call).
+     The LM is synthetic and sized like an AISHELL character LM (tools/lm_beam_bench.py's: ~1 M n-grams over the 3246 tokens, a
+     32 MiB table), its values arbitrary: the searches with it take other paths through the vocabulary, not fewer steps."""
+import argparse
 import os
 import sys
 import time
@@ -73,7 +80,24 @@ def kernel_leg(T):
     print(f"  states written per step: {R * T * C * 16 / 2 ** 20:.1f} MiB")
 
 
-def search_leg():
+def lm_leg(lm):
+    g = torch.Generator().manual_seed(13)
+    R, depth = B * BEAM, 12
+    tokens = torch.randint(1, V - 1, (R, depth), generator=g).to(DEV)
+    lens = torch.full((R,), depth, dtype=torch.int32, device=DEV)
+    _, cand = ops.topk_rows(ops.log_softmax_rows((torch.randn(R, V, generator=g) * 3.0).to(DEV)), C)
+    print(f"(iii) oe_ngram_next: order {lm.order}, {lm.n_ngrams} n-grams, table {lm.capacity * 16 / 2 ** 20:.0f} MiB, max_probe {lm.max_probe}; "
+          f"{R} hypotheses {depth} tokens deep")
+    runs = {f"every token ({V})": [], f"{C} candidates": []}
+    for _ in range(3):
+        runs[f"every token ({V})"].append(timed(lambda: ops.ngram_next(lm, tokens, lens, None, V - 1)))
+        runs[f"{C} candidates"].append(timed(lambda: ops.ngram_next(lm, tokens, lens, cand, V - 1)))
+    for (name, r), n in zip(runs.items(), (R * V, R * C)):
+        mid = sorted(r)[1]
+        print(f"  {name}: {mid:8.1f} us per call = {mid * 1e3 / n:6.2f} ns per term (runs {', '.join('%.1f' % x for x in r)})")
+
+
+def search_leg(lm=None):
     torch.manual_seed(7)
     model = ASRModel(80, V, **MODEL_CONF).to(DEV).eval()
     g = torch.Generator().manual_seed(123)
@@ -91,6 +115,10 @@ def search_leg():
     legs = {"joint search, ctc_weight 0.3": lambda: model.ctc_attention_beam_search(feats, flen, BEAM, 0.3, ctc_candidates=C),
             "joint search, ctc_weight 0  ": lambda: model.ctc_attention_beam_search(feats, flen, BEAM, 0.0, ctc_candidates=C),
             "recognize                   ": lambda: model.recognize(feats, flen, BEAM).tolist()}
+    if lm is not None:
+        for name, pre in (("joint search, 0.3 + LM, prebeam", True), ("joint search, 0.3 + LM, top-C  ", False)):
+            legs[name] = lambda pre=pre: model.ctc_attention_beam_search(feats, flen, BEAM, 0.3, ctc_candidates=C, lm=lm, lm_weight=0.5,
+                                                                         lm_prebeam=pre)
     runs = {k: [] for k in legs}
     with torch.no_grad():
         for it in range(4):
@@ -106,11 +134,24 @@ def search_leg():
         mean_len = sum(len([t for t in h if t != V - 1]) for h in out[name]) / B
         print(f"  {name}: {mids[name] * 1e3:8.1f} ms = {mids[name] * 1e6 / steps:7.1f} us per step, mean output {mean_len:.1f} tokens "
               f"(runs {', '.join('%.1f' % (x * 1e3) for x in r)})")
-    a, b, c = mids.values()
+    a, b, c = list(mids.values())[:3]
+    for name in list(mids)[3:]:
+        print(f"  {name.strip()} / joint (0.3): {mids[name] / a:.3f};  the LM side of a step: {(mids[name] - a) * 1e6 / steps:.1f} us")
     print(f"  joint (0.3) / recognize: {a / c:.2f};  joint (0) / recognize: {b / c:.2f};  the CTC side of a step: {(a - b) * 1e6 / steps:.1f} us")
 
 
 if __name__ == "__main__":
     assert torch.cuda.is_available(), "this tool measures on the GPU"
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lm-order", type=int, default=0, help="also time oe_ngram_next and the search with a synthetic n-gram LM of this order (2..5; 0: off)")
+    args = ap.parse_args()
+    if args.lm_order and not 2 <= args.lm_order <= 5:
+        ap.error("--lm-order takes 0 or 2..5")
+    lm = None
+    if args.lm_order:
+        from lm_beam_bench import synthetic_lm                      # beside this file
+        lm = synthetic_lm(args.lm_order).to(DEV)
     kernel_leg(SECONDS * 25 - 1)
-    search_leg()
+    if lm is not None:
+        lm_leg(lm)
+    search_leg(lm)
