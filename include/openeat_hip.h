@@ -421,6 +421,48 @@ int oe_ctc_align(const float* logits, long ldv, int B, int T, int V, const int* 
                  const int* tlens, int* frames, int* tok_start, int* tok_end, float* tok_logp, float* score, void* workspace,
                  void* stream);
 
+/* Long-form CTC segmentation on device (CTC segmentation, Kuerzinger et al. 2020): the best path of a WHOLE RECORDING through
+ * the trellis of its transcript - the utterances' labels concatenated - with the audio outside the transcript (intro, outro,
+ * music, noise) free.  With Tb = hlens[b], y = targets[b, :tlens[b]] (L labels), lp, ext[s], S = 2L+1, the legal moves (stay,
+ * step, skip) and the tie rule exactly as oe_ctc_align above (a predecessor replaces the best only if strictly greater, tried
+ * in the order stay, step, skip; the end state 2L is kept unless 2L-1 is strictly greater), two flags change the recursion:
+ *   free_start: state 0 costs nothing: v[t,0] = 0 for every t, t = 0 included.  Every other state follows oe_ctc_align's
+ *        recursion (v[0,1] = lp[0,ext[1]]; state 1 may be entered from state 0 at any frame).
+ *   free_end: staying in state 2L costs nothing and entering it costs the blank:
+ *        v[t,2L] = max(v[t-1,2L], v[t-1,2L-1] + lp[t,0]), the step only if strictly greater (v[0,2L] = -inf for L > 0).
+ *        L == 0 with free_start: the state-0 rule applies.  L == 0 with free_end only: v[0,0] = lp[0,0], the rest is free.
+ *   A frame of the returned path is FREE if (free_start and state_t == 0) or (free_end and t > 0 and state_t == state_{t-1} == 2L).
+ *   With both flags 0 the path problem is exactly oe_ctc_align's.  Feasibility does not change under the flags: infeasible is
+ *   Tb == 0 or fewer frames than L + adjacent repeats; the outputs are then -inf / -1 / 0 as in oe_ctc_align.
+ *   out (device memory):
+ *        frames (B, T) int32 = ext[state_t], -1 for t >= Tb;
+ *        path_logp (B, T) float32 or NULL = lp[t, ext[state_t]] in natural log, 0 on free frames and for t >= Tb;
+ *        tok_start / tok_end / tok_logp (B, Lmax), each or NULL, as oe_ctc_align defines them;
+ *        score (B) FLOAT64 = the path's log-probability: the float64 sum, in frame order, of the path_logp values; -inf if infeasible.
+ *   A property, not a defect: a free state costs 0 and every scored frame costs less than 0, so under free_start the path
+ *   leaves state 0 as late as it can and the first label's span comes out as short as optimality allows - the behaviour of
+ *   CTC segmentation as published.
+ *   The recursion accumulates in float32: the returned path is optimal up to float32 rounding of v (its float64 score is within
+ *   a relative 1e-4 of the float64 optimum in the tests), and it is always a legal path that collapses to y.
+ *   Labels are expected in [1, V); one outside [0, V) is read as the nearest valid column, never out of bounds.
+ *   Limits: 1 <= B, 1 <= T <= 2^20, 0 <= Lmax <= 8191, V > 1, ldv >= V.  Anything else, and any NULL required pointer
+ *   (logits, hlens, tlens, frames, score, workspace; targets unless Lmax == 0), is reported through oe_last_error before
+ *   any launch, with the outputs untouched.
+ *   workspace: oe_ctc_segment_workspace_bytes(B,T,V,Lmax) bytes, 16-byte aligned (0 for shapes outside the limits): 2 bits of
+ *        back-pointer per cell and 12 bytes per frame - never a float per cell, never a T x S table:
+ *        <= B * (T * (Sp/2 + 4*V + 64) + 65536) with Sp = 2*Lmax+1 rounded up to a multiple of 128.
+ * Two launches (row statistics; one workgroup per recording: recursion, back-trace, spans, score).  No workgroup waits for
+ * another, no atomics; no allocation, no host read, no host-side state: capturable. */
+typedef struct oe_ctc_segment_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens; const int* targets; int Lmax; const int* tlens;
+    int free_start, free_end;
+    int* frames; float* path_logp; int* tok_start; int* tok_end; float* tok_logp; double* score;
+    void* workspace;
+} oe_ctc_segment_args;
+size_t oe_ctc_segment_workspace_bytes(int B, int T, int V, int Lmax);
+int oe_ctc_segment(const oe_ctc_segment_args* args, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

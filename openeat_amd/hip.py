@@ -198,7 +198,16 @@ class PrefixBeamArgs(C.Structure):
                 ("out_score", c_fp), ("out_ctc", c_fp), ("out_lm", c_fp), ("out_bias", c_fp)]
 
 
-I, L, F, D, P, U64, SZ = C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
+class CtcSegmentArgs(C.Structure):
+    """oe_ctc_segment_args (include/openeat_hip.h); filled by ops.ctc_segment."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("targets", c_fp), ("Lmax", C.c_int), ("tlens", c_fp),
+                ("free_start", C.c_int), ("free_end", C.c_int),
+                ("frames", c_fp), ("path_logp", c_fp), ("tok_start", c_fp), ("tok_end", c_fp), ("tok_logp", c_fp), ("score", c_fp),
+                ("workspace", c_fp)]
+
+
+I, L, F, D, P, U64, SZ =C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
     "oe_abi_version": (I, []),
@@ -243,6 +252,8 @@ _SIGNATURES = {
     "oe_ctc_greedy": (I, [P, L, I, I, I, P, I, P, P, P, P]),
     "oe_ctc_align_workspace_bytes": (SZ, [I, I, I]),
     "oe_ctc_align": (I, [P, L, I, I, I, P, P, I, P, P, P, P, P, P, P, P]),
+    "oe_ctc_segment_workspace_bytes": (SZ, [I, I, I, I]),
+    "oe_ctc_segment": (I, [C.POINTER(CtcSegmentArgs), P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),

@@ -302,6 +302,90 @@ class ASRModel(torch.nn.Module):
         return out
 
     @torch.no_grad()
+    def ctc_logits_windowed(self, features: torch.Tensor, features_length: torch.Tensor, window: Optional[int], margin: int = 16):
+        """CTC logits of whole recordings, longer than one attention pass holds -> (logits (B, T', V), lens (B)).  Each
+        recording is cut by utils.segment.window_plan into kept spans of `window` encoder frames computed with `margin` frames of
+        context on either side; the windows of one recording go through _encode and ctc.logits as ONE batch (in plan order,
+        zero-padded to the longest), and their kept frames are copied to their place.  window None, or at or above every
+        recording's T': one plain pass over the batch."""
+        from openeat_amd.utils.segment import encoder_frames, window_plan
+        embed = self.encoder.embed
+        rate, rc = embed.subsampling_rate, embed.right_context
+        n_feats = [int(n) for n in features_length.tolist()]
+        n_enc = [encoder_frames(n, rate, rc) for n in n_feats]
+        if window is None or window >= max(n_enc):
+            encoder_out, encoder_mask, _ = self._encode(features, features_length)
+            return self.ctc.logits(encoder_out), encoder_mask.squeeze(1).sum(1)
+        out = None
+        for b, n in enumerate(n_feats):
+            plan = window_plan(n, window, margin, rate, rc)
+            flen = torch.tensor([f1 - f0 for f0, f1, _, _, _ in plan], dtype=features_length.dtype, device=features.device)
+            batch = features.new_zeros(len(plan), int(flen.max()), features.shape[2])
+            for w, (f0, f1, _, _, _) in enumerate(plan):
+                batch[w, : f1 - f0] = features[b, f0:f1]
+            encoder_out, _, _ = self._encode(batch, flen)
+            lg = self.ctc.logits(encoder_out)
+            if out is None:
+                out = lg.new_zeros(len(n_feats), max(n_enc), lg.shape[2])
+            for w, (_, _, q0, q1, o0) in enumerate(plan):
+                out[b, o0:o0 + q1 - q0] = lg[w, q0:q1]
+        return out, torch.tensor(n_enc, dtype=torch.int64, device=features.device)
+
+    @torch.no_grad()
+    def ctc_segment(self, features: torch.Tensor, features_length: torch.Tensor, utterances, window: Optional[int] = None,
+                    margin: int = 16, free_start: bool = True, free_end: bool = True, score_window: int = 30,
+                    with_times: bool = False, frame_shift_ms: float = 10):
+        """Long-form CTC segmentation (the reference has none; semantics in include/openeat_hip.h): each recording is aligned to
+        the concatenation of its utterances, utterances[b] a list of token-id lists, with the audio before / after the
+        transcript free.  Logits by ctc_logits_windowed (window None: one plain pass), recursion and back-trace on the device,
+        one D2H copy of the results.  Per recording {"score": log-prob of the path, "utterances": [{"start_frame",
+        "end_frame" (inclusive encoder frames), "mean_logp", "min_logp" (utils.segment.segment_stats over score_window frames),
+        "confidence" = exp(min_logp), and with_times "start_s" / "end_s"}]}; None for a recording whose transcript does not
+        fit its frames."""
+        from openeat_amd.utils.segment import segment_stats
+        B = features.shape[0]
+        assert B == features_length.shape[0] == len(utterances)
+        if any(len(u) == 0 for rec in utterances for u in rec) or any(len(rec) == 0 for rec in utterances):
+            raise ValueError("ctc_segment: every recording needs utterances and every utterance labels")
+        logits, lens = self.ctc_logits_windowed(features, features_length, window, margin)
+        dev = logits.device
+        offsets = [[0] for _ in range(B)]
+        for b, rec in enumerate(utterances):
+            for u in rec:
+                offsets[b].append(offsets[b][-1] + len(u))
+        Lmax = max(o[-1] for o in offsets)
+        ys = torch.zeros(B, Lmax, dtype=torch.int64)
+        for b, rec in enumerate(utterances):
+            ys[b, : offsets[b][-1]] = torch.tensor([t for u in rec for t in u], dtype=torch.int64)
+        ylens = torch.tensor([o[-1] for o in offsets], dtype=torch.int32)
+        _, T, V = logits.shape
+        _, path_logp, start, end, _, score = ops.ctc_segment(logits, V, B, T, V, lens, ys.to(dev), ylens.to(dev), free_start, free_end)
+        cols = []
+        for b in range(B):
+            L = offsets[b][-1]
+            st = segment_stats(path_logp[b], start[b, :L], end[b, :L], offsets[b], score_window)
+            cols += [score[b:b + 1]] + [c.double() for c in st]
+        packed = torch.cat(cols).cpu().tolist()
+        rate = self.encoder.embed.subsampling_rate
+        out, at = [], 0
+        for b in range(B):
+            U = len(utterances[b])
+            sc, s, e, mean, mn = packed[at], *(packed[at + 1 + i * U: at + 1 + (i + 1) * U] for i in range(4))
+            at += 1 + 4 * U
+            if sc == float("-inf"):
+                out.append(None)
+                continue
+            segs = []
+            for u in range(U):
+                seg = {"start_frame": int(s[u]), "end_frame": int(e[u]), "mean_logp": mean[u], "min_logp": mn[u],
+                       "confidence": math.exp(mn[u])}
+                if with_times:
+                    seg["start_s"], seg["end_s"] = frame_times(int(s[u]), int(e[u]), rate, frame_shift_ms)
+                segs.append(seg)
+            out.append({"score": sc, "utterances": segs})
+        return out
+
+    @torch.no_grad()
     def error_counts(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
                      targets_length: torch.Tensor, mode: str = "ctc_greedy_search", beam_size: int = 10,
                      nbest_oracle: bool = False, **decode_kwargs) -> dict:

@@ -44,3 +44,12 @@ class CTC(torch.nn.Module):
         lg = self.logits(hs_pad)
         B, T, V = lg.shape
         return ops.ctc_align(lg, V, B, T, V, hlens, ys_pad, ys_lens)
+
+    def segment(self, hs_pad: torch.Tensor, hlens: torch.Tensor, ys_pad: torch.Tensor, ys_lens: torch.Tensor,
+                free_start: bool = True, free_end: bool = True):
+        """Best CTC path of each whole recording through its concatenated transcript, the audio before / after it free
+        (CTC segmentation; the reference has none).  Returns device tensors (frames, path_logp, start, end, tok_logp,
+        score), see ops.ctc_segment."""
+        lg = self.logits(hs_pad)
+        B, T, V = lg.shape
+        return ops.ctc_segment(lg, V, B, T, V, hlens, ys_pad, ys_lens, free_start, free_end)

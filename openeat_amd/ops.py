@@ -2364,6 +2364,39 @@ def ctc_align(logits, ldv, B, T, V, hlens, ys, ylens):
     return frames, start[:, :Lmax], end[:, :Lmax], tok_logp[:, :Lmax], score
 
 
+def ctc_segment(logits, ldv, B, T, V, hlens, ys, ylens, free_start=True, free_end=True):
+    """Long-form CTC segmentation (oe_ctc_segment; semantics in include/openeat_hip.h): logits (B, T, ldv) float32 of whole
+    recordings, ys (B, Lmax <= 8191) the recordings' concatenated labels of which ylens[b] count; free_start / free_end make
+    the audio before / after the transcript free -> device tensors (frames (B, T) int32, path_logp (B, T) float32,
+    start (B, Lmax) int32, end (B, Lmax) int32, tok_logp (B, Lmax) float32, score (B) float64)."""
+    logits = _chk(logits, "ctc_segment")
+    dev = logits.device
+    Lmax = int(ys.shape[1])
+    ys32 = ys.to(torch.int32).contiguous()
+    if Lmax == 0:                               # the C ABI wants a row per recording; nothing of it is read
+        ys32 = torch.zeros(B, 1, dtype=torch.int32, device=dev)
+    Lk = max(Lmax, 1)
+    hl32, yl32 = hlens.to(torch.int32).contiguous(), ylens.to(torch.int32).contiguous()
+    frames = torch.empty(B, T, dtype=torch.int32, device=dev)
+    path_logp = torch.empty(B, T, dtype=torch.float32, device=dev)
+    start = torch.empty(B, Lk, dtype=torch.int32, device=dev)
+    end = torch.empty(B, Lk, dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(B, Lk, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    nbytes = hip.lib().oe_ctc_segment_workspace_bytes(B, T, V, Lk)
+    if nbytes == 0:
+        raise ValueError(f"ctc_segment: B={B} T={T} Lmax={Lmax} outside 1 <= B, 1 <= T <= 2^20, Lmax <= 8191")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = hip.CtcSegmentArgs()
+    a.logits, a.ldv, a.B, a.T, a.V = logits.data_ptr(), ldv, B, T, V
+    a.hlens, a.targets, a.Lmax, a.tlens = hl32.data_ptr(), ys32.data_ptr(), Lk, yl32.data_ptr()
+    a.free_start, a.free_end = int(bool(free_start)), int(bool(free_end))
+    a.frames, a.path_logp, a.tok_start, a.tok_end = frames.data_ptr(), path_logp.data_ptr(), start.data_ptr(), end.data_ptr()
+    a.tok_logp, a.score, a.workspace = tok_logp.data_ptr(), score.data_ptr(), ws.data_ptr()
+    hip.check(hip.lib().oe_ctc_segment(hip.C.byref(a), hip.stream()), "oe_ctc_segment")
+    return frames, path_logp, start[:, :Lmax], end[:, :Lmax], tok_logp[:, :Lmax], score
+
+
 def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
     """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
     openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:
