@@ -873,6 +873,64 @@ typedef struct oe_prefix_beam_args {
 } oe_prefix_beam_args;
 size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam);
 int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream);
+/* The same search, resumable: it takes the frames of an utterance chunk by chunk and carries everything it knows in a device
+ * state, for recordings whose frames arrive window by window and whose back-pointers would not fit as a whole.  The four
+ * variants are those of oe_ctc_prefix_beam (lm / ctx of `search`), from the same kernel source.
+ *
+ * search: the oe_prefix_beam_args of THIS chunk - topk_logp / topk_idx (B, Tmax, beam), lens (B) the frames of this chunk
+ *   (0 allowed; NULL: Tmax), beam, max_len, lm, ctx, the weights, eos, final, the out_* and a workspace of
+ *   oe_ctc_prefix_beam_workspace_bytes(B, Tmax, beam) bytes: the back-pointers are those of the chunk, never of the recording.
+ *   Its last word is the status word, zeroed and read by the caller as for the one-shot search.
+ * The state, oe_ctc_prefix_beam_state_bytes(B, beam, max_len) bytes of device memory (the size is the same for every
+ *   variant), is opaque.  Per utterance it carries what the frame loop keeps between two frames - the number of live
+ *   prefixes, the number of frames consumed so far, per slot key, pb, pnb, len, last, with an LM lm, ent[], bo[], with a graph
+ *   hits, the automaton state, pend - and every slot's tail: the tokens and emission frames behind the stable prefix.  Its
+ *   header records B, beam, max_len and the variant (LM / graph); the kernel checks it against the call and on a mismatch
+ *   writes 2 into the status word and touches no output, no state and no stable buffer.  The LM entry numbers and the
+ *   automaton states are indices into the tables of the model and the graph: a state is valid only with the SAME model and the
+ *   SAME graph (and weights) it was made with, which nothing checks.
+ * A chunk resumes the frame loop at state_in (NULL: the search starts here, with the empty prefix) and runs lens[b] frames.
+ *   Without `last` it saves the state to state_out and does nothing else to the scores.  lens[b] == 0 carries utterance b
+ *   through untouched: so a batch of recordings of different lengths ends together in one `last` call.  state_out must not be
+ *   state_in (the tails are read from one while the other is written): the caller keeps two and swaps them.
+ * With `last` the end-of-utterance steps run exactly as in the one-shot search: the </s> term, the pending hotword credit
+ *   dropped if final, the stable re-sort.  For ANY sequence of chunks whose frames concatenate to an utterance - chunks of one
+ *   frame, of zero frames, a single chunk with state_in == NULL and last - out_prefix (its used part) / out_len / out_score /
+ *   out_ctc / out_lm / out_bias are bit for bit what oe_ctc_prefix_beam writes for that utterance.  state_out may be NULL
+ *   with last; the stable buffers are then left as they are.
+ * Stable prefix.  After every chunk with a state_out, stable_len[b] is the length of the longest common prefix of utterance
+ *   b's live prefixes.  Every later prefix extends a live one, so these tokens never change and stable_len never shrinks.
+ *   Newly stable tokens and their frames are appended to stable_prefix / stable_frame (B, max_len), which the caller owns
+ *   and only the kernel appends to; the caller zeroes stable_len (B) before the first chunk.  The tails of the state shrink
+ *   by what was committed, so a chunk's work is proportional to its frames plus the tail lengths, not to the transcript so
+ *   far (an emitting chunk also writes the n-best rows in full).
+ * Emission frame.  The emission frame of a token is the global frame index t, counted over all chunks, at which the prefix
+ *   ending in that token was created as a new entry on the slot's back-pointer chain (the frame whose record carries the
+ *   token).  A prefix that stays, or that an extension lands on, keeps its frames; one that dropped out of the beam and is
+ *   created again has the later frame.  Frames are strictly increasing along a prefix.  The chains of two live prefixes can
+ *   disagree about the frame of a shared token (one went through the prefix before it dropped out, the other through its
+ *   re-creation): the stable prefix commits the earliest, and out_frame reports committed tokens with the committed frame.
+ * emit without last: the n-best is written in the search's own order with the running totals as the pruning key sees them -
+ *   no </s> term, the pending credit kept; missing slots -1 / -inf as in the one-shot search; out_prefix is the stable prefix
+ *   followed by the tail, out_frame (B, beam, max_len) or NULL the emission frame of each of its tokens.  With last the outputs
+ *   are always written.  A prefix longer than max_len sets the status word to 1, as in the one-shot search; the state is then
+ *   of no further use.
+ * Checked before any launch and reported through oe_last_error: a null chunk or search, everything oe_ctc_prefix_beam
+ *   checks, state_out == NULL without last, state_in == state_out, a null stable_prefix / stable_frame / stable_len.  One
+ *   launch, no atomics other than the status word, no allocation, no host read: capturable. */
+typedef struct oe_prefix_beam_chunk {
+    const oe_prefix_beam_args* search;
+    const void* state_in;         /* NULL: the search starts here */
+    void* state_out;              /* NULL allowed only with last; never state_in */
+    int last;                     /* the audio of every utterance ends with this chunk */
+    int emit;                     /* write the n-best outputs for this chunk (always done when last) */
+    int* stable_prefix;           /* (B, max_len) */
+    int* stable_frame;            /* (B, max_len) */
+    int* stable_len;              /* (B) in/out */
+    int* out_frame;               /* (B, beam, max_len) or NULL */
+} oe_prefix_beam_chunk;
+size_t oe_ctc_prefix_beam_state_bytes(int B, int beam, int max_len);
+int oe_ctc_prefix_beam_chunk(const oe_prefix_beam_chunk* chunk, void* stream);
 /* CTC prefix beam search, HOST code (all pointers are host pointers): the per-frame recursion of
  * asr_model.py:359-396 on the top-`beam` (log-prob, token) pairs of every frame (computed on the
  * device).  Doubles and insertion-ordered stable pruning as in the reference's Python, so the

@@ -1,6 +1,9 @@
 // CTC prefix beam search on the device, one wavefront per utterance, plain, with n-gram LM shallow fusion and with hotword
-// biasing: one kernel source, template <bool LM, bool CTX>, one entry point (oe_ctc_prefix_beam: its oe_prefix_beam_args name
-// the n-gram model and the context graph, or neither; semantics in include/openeat_hip.h).
+// biasing: one kernel source, template <bool LM, bool CTX, bool CHUNK>, one entry point for the search over a whole utterance
+// (oe_ctc_prefix_beam: its oe_prefix_beam_args name the n-gram model and the context graph, or neither; semantics in
+// include/openeat_hip.h) and one for the resumable search, which takes the frames chunk by chunk and carries a device state
+// between them (oe_ctc_prefix_beam_chunk, CHUNK = true: the same frame loop, entered from a saved state and left into one; what
+// it adds is described above the kernel and sits under `if constexpr (CHUNK)`).
 // (the reference's openeat/models/asr_model.py:359-396: the per-frame Python dict loop).
 //
 // Same arithmetic and the same ordering as the reference and as the host implementation (beam_host.cpp, which stays as
@@ -198,10 +201,58 @@ __device__ __forceinline__ int pb_ctx_step(const PbCtxArgs& g, int state, int to
     return ns;
 }
 
-template <bool LM, bool CTX>
+// ---- the resumable search (CHUNK = true; oe_ctc_prefix_beam_chunk, semantics in include/openeat_hip.h) -------------------
+// The state of a search between two chunks, device memory: a header of 8 ints (magic, B, beam, max_len, variant = LM | CTX << 1)
+// and per utterance, struct of arrays over the beam slots, what the frame loop keeps in LDS - key, pb, pnb, lm, hits (8 bytes
+// each), len, last, cstate, cpend, ent[PB_H], bo[PB_H] (4 bytes each) - then ncur and the frames consumed, then every slot's
+// tokens and emission frames, (beam, max_len) each, INDEXED BY THE POSITION IN THE PREFIX: a slot's tail is the positions
+// stable_len .. len-1 of its row, what lies in front of them is not kept up.  So committing tokens to the stable prefix moves
+// nothing, and a chunk copies, per slot, the tail of the slot it grew from out of state_in and appends its own tokens.
+// The size does not depend on the variant: one pair of states serves any search of that beam and max_len.
+#define PB_STATE_MAGIC 0x70624353
+#define PB_STATE_HEADER 32
+
+struct PbChunkArgs {    // what the resumable search takes on top (empty for CHUNK = false)
+    const void* state_in;
+    void* state_out;
+    int last, emit;
+    int* __restrict__ stable_prefix;
+    int* __restrict__ stable_frame;
+    int* __restrict__ stable_len;
+    int* __restrict__ out_frame;
+};
+struct PbNoChunk {};
+template <bool CHUNK> struct PbChunkOf { typedef PbNoChunk type; };
+template <> struct PbChunkOf<true> { typedef PbChunkArgs type; };
+
+struct PbState {        // one utterance's part of a state
+    unsigned long long* key;
+    double *pb, *pnb, *lm, *hits;
+    int *len, *last, *cstate, *cpend, *ent;
+    float* bo;
+    int *misc, *tail_tok, *tail_frame;
+};
+__host__ __device__ inline size_t pb_state_utt_bytes(int beam, int max_len) {
+    return (size_t)beam * 40 + ((size_t)beam * (4 + 2 * PB_H) + 2) * 4 + (size_t)beam * (size_t)max_len * 8;
+}
+__device__ __forceinline__ PbState pb_state_of(const void* base, int b, int beam, int max_len) {
+    char* p = (char*)base + PB_STATE_HEADER + (size_t)b * pb_state_utt_bytes(beam, max_len);
+    PbState s;
+    s.key = (unsigned long long*)p;
+    s.pb = (double*)p + beam; s.pnb = s.pb + beam; s.lm = s.pnb + beam; s.hits = s.lm + beam;
+    int* q = (int*)(s.hits + beam);
+    s.len = q; s.last = q + beam; s.cstate = q + 2 * beam; s.cpend = q + 3 * beam; s.ent = q + 4 * beam;
+    s.bo = (float*)(s.ent + beam * PB_H);
+    s.misc = s.ent + 2 * beam * PB_H;
+    s.tail_tok = s.misc + 2;
+    s.tail_frame = s.tail_tok + (size_t)beam * (size_t)max_len;
+    return s;
+}
+
+template <bool LM, bool CTX, bool CHUNK>
 __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __restrict__ topk_logp, const long long* __restrict__ topk_idx,
                                                              int Tmax, const int* __restrict__ lens, int beam, int max_len,
-                                                             typename PbArgsOf<CTX>::type la,
+                                                             typename PbArgsOf<CTX>::type la, typename PbChunkOf<CHUNK>::type ck,
                                                              int* __restrict__ hist, int* __restrict__ out_prefix,
                                                              int* __restrict__ out_len, double* __restrict__ out_score,
                                                              int* __restrict__ status) {
@@ -228,7 +279,36 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
     const int T = min(lens ? lens[b] : Tmax, Tmax);
     const double NEG = pb_neg();
     int ncur = 1;
-    if (lane == 0) {
+    int t0 = 0;                                                    // CHUNK: frames consumed by the chunks before this one
+    bool fresh = true;
+    if constexpr (CHUNK) {
+        if (ck.state_in) {                                         // resume: the header must be this call's, then LDS is reloaded
+            fresh = false;
+            const int* hd = (const int*)ck.state_in;
+            if (hd[0] != PB_STATE_MAGIC || hd[1] != (int)gridDim.x || hd[2] != beam || hd[3] != max_len ||
+                hd[4] != ((LM ? 1 : 0) | (CTX ? 2 : 0))) {
+                if (lane == 0) atomicExch(status, 2);
+                return;                                            // block-uniform, before any output
+            }
+            const PbState si = pb_state_of(ck.state_in, b, beam, max_len);
+            ncur = min(max(si.misc[0], 0), beam);
+            t0 = si.misc[1];
+            if (lane < ncur) {
+                cur_key[lane] = si.key[lane]; cur_pb[lane] = si.pb[lane]; cur_pnb[lane] = si.pnb[lane]; cur_len[lane] = si.len[lane];
+                cur_last[lane] = si.last[lane];
+                if constexpr (LM) {
+                    cur_lm[lane] = si.lm[lane];
+#pragma unroll
+                    for (int j = 0; j < PB_H; ++j) { cur_ent[lane][j] = si.ent[lane * PB_H + j]; cur_bo[lane][j] = si.bo[lane * PB_H + j]; }
+                }
+                if constexpr (CTX) {
+                    const int cs = si.cstate[lane];                // indexes the graph's tables: a state of another graph stays inside
+                    cur_hits[lane] = si.hits[lane]; cur_cstate[lane] = (unsigned)cs < (unsigned)la.n_states ? cs : 0; cur_cpend[lane] = si.cpend[lane];
+                }
+            }
+        }
+    }
+    if (fresh && lane == 0) {
         cur_key[0] = 0; cur_pb[0] = 0.0; cur_pnb[0] = NEG; cur_len[0] = 0; cur_last[0] = -1;
         if constexpr (LM) {
             cur_lm[0] = 0.0;
@@ -397,16 +477,19 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
 
     // ---- LM / CTX, end of the utterance: the </s> term, the pending credit dropped if final, then the survivors stably
     // re-sorted by total
+    // CHUNK, not the last chunk: neither of the two, so the totals are the running ones the pruning key saw and the order stays
+    bool ended = true;
+    if constexpr (CHUNK) ended = ck.last != 0;
     double lm = 0.0, ctc = NEG, total = NEG, bias = 0.0;
     if constexpr (LM || CTX) {
         if (lane < ncur) {
             if constexpr (LM) {
                 lm = cur_lm[lane];
-                if (la.eos) lm = lm + pb_extend(la.m, cur_ent[lane], cur_bo[lane], la.m.eos_word, nullptr, nullptr);
+                if (la.eos && ended) lm = lm + pb_extend(la.m, cur_ent[lane], cur_bo[lane], la.m.eos_word, nullptr, nullptr);
             }
             ctc = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
             if constexpr (CTX) {
-                bias = la.final ? cur_hits[lane] : pb_bias(cur_hits[lane], la.c, cur_cpend[lane]);
+                bias = (la.final && ended) ? cur_hits[lane] : pb_bias(cur_hits[lane], la.c, cur_cpend[lane]);
                 total = pb_total_ctx<LM>(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus, bias);
             } else {
                 total = pb_total(ctc, lm, cur_len[lane], la.lm_weight, la.length_bonus);
@@ -414,6 +497,172 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const float* __rest
             fin_total[lane] = total;
         }
         __syncthreads();
+    }
+
+    if constexpr (CHUNK) {
+        // ---- the end of a chunk.  Every slot's row of tokens and frames (position-indexed) is put together where it will
+        // stay: in state_out, or, without one (the last chunk only), directly in its rank's rows of out_prefix / out_frame.
+        __shared__ int fin_org[PB_MAXBEAM], fin_row[PB_MAXBEAM];
+        const bool outw = ck.last || ck.emit;
+        const bool keep = ck.state_out != nullptr;
+        const int S0 = fresh ? 0 : min(max(ck.stable_len[b], 0), max_len);          // committed so far
+        const long ub = (long)b * beam;
+        PbState si{}, so{};
+        if (!fresh) si = pb_state_of(ck.state_in, b, beam, max_len);
+        if (keep) so = pb_state_of(ck.state_out, b, beam, max_len);
+        // (A) lane = slot: the scores, then the chunk's back-pointers walked to its first frame: the tokens it appended go to
+        // their positions, and the slot of state_in the prefix grew from is what is left
+        if (lane < beam) {
+            if (lane < ncur) {
+                int rank = lane;
+                if constexpr (LM || CTX) {
+                    rank = 0;
+                    for (int i = 0; i < ncur; ++i) {
+                        const double ti = fin_total[i];
+                        if (ti > total || (ti == total && i < lane)) ++rank;
+                    }
+                }
+                const long o = ub + rank;
+                const int len = cur_len[lane];
+                if (outw) {
+                    if constexpr (CTX) {
+                        out_score[o] = total;
+                        la.out_ctc[o] = ctc;
+                        if constexpr (LM) la.out_lm[o] = lm;
+                        la.out_bias[o] = bias;
+                    } else if constexpr (LM) {
+                        out_score[o] = total;
+                        la.out_ctc[o] = ctc;
+                        la.out_lm[o] = lm;
+                    } else {
+                        out_score[o] = pb_log_add2(cur_pb[lane], cur_pnb[lane]);
+                    }
+                    out_len[o] = len;
+                }
+                if (len > max_len) atomicExch(status, 1);
+                int* dtok = keep ? so.tail_tok + (size_t)lane * max_len : out_prefix + o * max_len;
+                int* dfr = keep ? so.tail_frame + (size_t)lane * max_len : (ck.out_frame ? ck.out_frame + o * max_len : nullptr);
+                int slot = lane, pos = len - 1;
+                for (int t = T - 1; t >= 0; --t) {
+                    const int parent = hist_b[((long)t * beam + slot) * 2], tok = hist_b[((long)t * beam + slot) * 2 + 1];
+                    if (tok >= 0) {
+                        if (pos >= 0 && pos < max_len) {
+                            dtok[pos] = tok;
+                            if (dfr) dfr[pos] = t0 + t;
+                        }
+                        --pos;
+                    }
+                    slot = parent;
+                }
+                fin_org[lane] = slot;
+                fin_row[lane] = rank;
+            } else if (outw) {
+                const long o = ub + lane;
+                out_score[o] = NEG;
+                if constexpr (LM) { la.out_ctc[o] = NEG; la.out_lm[o] = NEG; }
+                if constexpr (CTX) {
+                    if constexpr (!LM) la.out_ctc[o] = NEG;
+                    la.out_bias[o] = NEG;
+                }
+                out_len[o] = -1;
+            }
+        }
+        __syncthreads();
+        // (B) the wave, slot by slot: the tail the prefix had when the chunk began, copied from the slot it grew from
+        if (!fresh) {
+            for (int s = 0; s < ncur; ++s) {
+                const int org = fin_org[s];
+                const int ol = min(si.len[org], max_len);
+                const long o = ub + fin_row[s];
+                int* dtok = keep ? so.tail_tok + (size_t)s * max_len : out_prefix + o * max_len;
+                int* dfr = keep ? so.tail_frame + (size_t)s * max_len : (ck.out_frame ? ck.out_frame + o * max_len : nullptr);
+                const int* stok = si.tail_tok + (size_t)org * max_len;
+                const int* sfr = si.tail_frame + (size_t)org * max_len;
+                for (int i0 = S0 + lane; i0 < ol; i0 += 64 * 8) {   // 16 independent loads in flight: one wave moves the whole tail
+                    int vt[8], vf[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int i = i0 + 64 * u;
+                        vt[u] = i < ol ? stok[i] : 0;
+                        vf[u] = i < ol ? sfr[i] : 0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int i = i0 + 64 * u;
+                        if (i < ol) {
+                            dtok[i] = vt[u];
+                            if (dfr) dfr[i] = vf[u];
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // (C) the stable prefix grows by what all live prefixes share behind it (lane = position, 64 at a time); where their
+        // chains disagree about a token's frame, the earliest one is committed
+        int S1 = S0;
+        if (keep && ncur > 0) {
+            int minlen = max_len;
+            for (int s = 0; s < ncur; ++s) minlen = min(minlen, cur_len[s]);
+            S1 = max(minlen, S0);
+            for (int base = S0; base < minlen; base += 64) {
+                const int i = base + lane;
+                bool differ = false;
+                int tok0 = 0, fmin = 0;
+                if (i < minlen) {
+                    tok0 = so.tail_tok[i]; fmin = so.tail_frame[i];
+                    for (int s = 1; s < ncur; ++s) {
+                        if (so.tail_tok[(size_t)s * max_len + i] != tok0) differ = true;
+                        fmin = min(fmin, so.tail_frame[(size_t)s * max_len + i]);
+                    }
+                }
+                const unsigned long long m = __ballot(differ);
+                const int first = m ? __ffsll((long long)m) - 1 : 64;
+                if (i < minlen && lane < first) {
+                    ck.stable_prefix[(long)b * max_len + i] = tok0;
+                    ck.stable_frame[(long)b * max_len + i] = fmin;
+                }
+                if (m) { S1 = base + first; break; }
+            }
+            if (lane == 0) ck.stable_len[b] = S1;
+        }
+        __syncthreads();
+        // (D) the n-best rows: the stable prefix, then the slot's own row
+        if (outw) {
+            for (int s = 0; s < ncur; ++s) {
+                if (cur_len[s] > max_len) continue;                // reported; the row is not written, as in the one-shot search
+                const long o = ub + fin_row[s];
+                const int n = keep ? cur_len[s] : S1;              // without a state (S1 = S0) the positions behind are in place already
+                const int* rtok = so.tail_tok + (size_t)s * max_len;
+                const int* rfr = so.tail_frame + (size_t)s * max_len;
+                for (int i = lane; i < n; i += 64) {
+                    out_prefix[o * max_len + i] = i < S1 ? ck.stable_prefix[(long)b * max_len + i] : rtok[i];
+                    if (ck.out_frame) ck.out_frame[o * max_len + i] = i < S1 ? ck.stable_frame[(long)b * max_len + i] : rfr[i];
+                }
+            }
+        }
+        // (E) what the frame loop carries
+        if (keep) {
+            if (lane < ncur) {
+                so.key[lane] = cur_key[lane]; so.pb[lane] = cur_pb[lane]; so.pnb[lane] = cur_pnb[lane]; so.len[lane] = cur_len[lane];
+                so.last[lane] = cur_last[lane];
+                if constexpr (LM) {
+                    so.lm[lane] = cur_lm[lane];
+#pragma unroll
+                    for (int j = 0; j < PB_H; ++j) { so.ent[lane * PB_H + j] = cur_ent[lane][j]; so.bo[lane * PB_H + j] = cur_bo[lane][j]; }
+                }
+                if constexpr (CTX) { so.hits[lane] = cur_hits[lane]; so.cstate[lane] = cur_cstate[lane]; so.cpend[lane] = cur_cpend[lane]; }
+            }
+            if (lane == 0) {
+                so.misc[0] = ncur; so.misc[1] = t0 + max(T, 0);
+                if (b == 0) {
+                    int* hd = (int*)ck.state_out;
+                    hd[0] = PB_STATE_MAGIC; hd[1] = (int)gridDim.x; hd[2] = beam; hd[3] = max_len; hd[4] = (LM ? 1 : 0) | (CTX ? 2 : 0);
+                    hd[5] = 0; hd[6] = 0; hd[7] = 0;
+                }
+            }
+        }
+        return;
     }
 
     // ---- results: scores, lengths, tokens by walking the back-pointers
@@ -468,20 +717,18 @@ static size_t pb_hist_words(int B, int Tmax, int beam) { return (size_t)B * (siz
 extern "C" size_t oe_ctc_prefix_beam_workspace_bytes(int B, int Tmax, int beam) { return (pb_hist_words(B, Tmax, beam) + 1) * sizeof(int); }
 
 // la: a PbCtxArgs; the two instantiations without a graph take its PbLmArgs part
-template <bool LM, bool CTX>
-static int pb_launch(const oe_prefix_beam_args& a, const typename PbArgsOf<CTX>::type& la, void* stream) {
+template <bool LM, bool CTX, bool CHUNK>
+static int pb_launch(const oe_prefix_beam_args& a, const typename PbArgsOf<CTX>::type& la, const typename PbChunkOf<CHUNK>::type& ck, void* stream) {
     int* hist = (int*)a.workspace;
     int* status = hist + pb_hist_words(a.B, a.Tmax, a.beam);      // the caller zeroes this word and reads it back
-    hipLaunchKernelGGL((ctc_prefix_beam_kernel<LM, CTX>), dim3(a.B), dim3(64), 0, (hipStream_t)stream, a.topk_logp, a.topk_idx, a.Tmax, a.lens,
-                       a.beam, a.max_len, la, hist, a.out_prefix, a.out_len, a.out_score, status);
-    OE_LAUNCH_CHECK("ctc_prefix_beam");
+    hipLaunchKernelGGL((ctc_prefix_beam_kernel<LM, CTX, CHUNK>), dim3(a.B), dim3(64), 0, (hipStream_t)stream, a.topk_logp, a.topk_idx, a.Tmax,
+                       a.lens, a.beam, a.max_len, la, ck, hist, a.out_prefix, a.out_len, a.out_score, status);
+    OE_LAUNCH_CHECK(CHUNK ? "ctc_prefix_beam_chunk" : "ctc_prefix_beam");
     return 0;
 }
 
-extern "C" int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream) {
-    const char* fn = "oe_ctc_prefix_beam";
-    OE_REQUIRE(args, "%s: null pointer (args)", fn);
-    const oe_prefix_beam_args& a = *args;
+// the checks of the search's arguments, shared by the two entry points; fills la
+static int pb_prepare(const char* fn, const oe_prefix_beam_args& a, PbCtxArgs& la) {
     const oe_ngram_model* lm = a.lm;
     const oe_context_graph* g = a.ctx;
     OE_REQUIRE(a.topk_logp && a.topk_idx && a.workspace && a.out_prefix && a.out_len && a.out_score, "%s: null pointer", fn);
@@ -492,7 +739,6 @@ extern "C" int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream)
     OE_REQUIRE(!g || (g->edges && g->fail && g->out && g->pend), "%s: null pointer (context graph)", fn);
     OE_REQUIRE(a.B > 0 && a.Tmax >= 0 && a.max_len >= 0, "%s: bad shape B=%d Tmax=%d max_len=%d", fn, a.B, a.Tmax, a.max_len);
     OE_REQUIRE(a.beam >= 1 && a.beam <= PB_MAXBEAM, "%s: beam must be 1..%d (got %d)", fn, PB_MAXBEAM, a.beam);
-    PbCtxArgs la{};
     if (lm) {
         if (ng_model_args(fn, lm, &la.m)) return -1;
         OE_REQUIRE(lm->V > 0, "%s: bad vocabulary size V=%d", fn, lm->V);
@@ -516,7 +762,41 @@ extern "C" int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream)
         la.fail = g->fail; la.out = (const int2*)g->out; la.pend = g->pend; la.n_states = g->n_states; la.c = g->c;
         la.final = a.final; la.out_bias = a.out_bias;
     }
-    if (!lm && !g) return pb_launch<false, false>(a, la, stream);
-    if (!g) return pb_launch<true, false>(a, la, stream);
-    return lm ? pb_launch<true, true>(a, la, stream) : pb_launch<false, true>(a, la, stream);
+    return 0;
+}
+
+extern "C" int oe_ctc_prefix_beam(const oe_prefix_beam_args* args, void* stream) {
+    const char* fn = "oe_ctc_prefix_beam";
+    OE_REQUIRE(args, "%s: null pointer (args)", fn);
+    const oe_prefix_beam_args& a = *args;
+    PbCtxArgs la{};
+    if (pb_prepare(fn, a, la)) return -1;
+    const PbNoChunk ck{};
+    if (!a.lm && !a.ctx) return pb_launch<false, false, false>(a, la, ck, stream);
+    if (!a.ctx) return pb_launch<true, false, false>(a, la, ck, stream);
+    return a.lm ? pb_launch<true, true, false>(a, la, ck, stream) : pb_launch<false, true, false>(a, la, ck, stream);
+}
+
+extern "C" size_t oe_ctc_prefix_beam_state_bytes(int B, int beam, int max_len) {
+    if (B <= 0 || beam < 1 || beam > PB_MAXBEAM || max_len < 0) return 0;
+    return PB_STATE_HEADER + (size_t)B * pb_state_utt_bytes(beam, max_len);
+}
+
+extern "C" int oe_ctc_prefix_beam_chunk(const oe_prefix_beam_chunk* chunk, void* stream) {
+    const char* fn = "oe_ctc_prefix_beam_chunk";
+    OE_REQUIRE(chunk, "%s: null pointer (chunk)", fn);
+    OE_REQUIRE(chunk->search, "%s: null pointer (search)", fn);
+    const oe_prefix_beam_args& a = *chunk->search;
+    PbCtxArgs la{};
+    if (pb_prepare(fn, a, la)) return -1;
+    OE_REQUIRE(chunk->state_out || chunk->last, "%s: state_out may be NULL with last only", fn);
+    OE_REQUIRE(!chunk->state_in || chunk->state_in != chunk->state_out, "%s: state_in and state_out must not alias", fn);
+    OE_REQUIRE(chunk->stable_prefix && chunk->stable_frame && chunk->stable_len, "%s: null pointer (stable_prefix / stable_frame / stable_len)", fn);
+    PbChunkArgs ck{};
+    ck.state_in = chunk->state_in; ck.state_out = chunk->state_out; ck.last = chunk->last != 0; ck.emit = chunk->emit != 0;
+    ck.stable_prefix = chunk->stable_prefix; ck.stable_frame = chunk->stable_frame; ck.stable_len = chunk->stable_len;
+    ck.out_frame = chunk->out_frame;
+    if (!a.lm && !a.ctx) return pb_launch<false, false, true>(a, la, ck, stream);
+    if (!a.ctx) return pb_launch<true, false, true>(a, la, ck, stream);
+    return a.lm ? pb_launch<true, true, true>(a, la, ck, stream) : pb_launch<false, true, true>(a, la, ck, stream);
 }

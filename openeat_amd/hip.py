@@ -198,6 +198,12 @@ class PrefixBeamArgs(C.Structure):
                 ("out_score", c_fp), ("out_ctc", c_fp), ("out_lm", c_fp), ("out_bias", c_fp)]
 
 
+class PrefixBeamChunk(C.Structure):
+    """oe_prefix_beam_chunk (include/openeat_hip.h); filled by prefix_beam_chunk."""
+    _fields_ = [("search", C.POINTER(PrefixBeamArgs)), ("state_in", c_fp), ("state_out", c_fp), ("last", C.c_int), ("emit", C.c_int),
+                ("stable_prefix", c_fp), ("stable_frame", c_fp), ("stable_len", c_fp), ("out_frame", c_fp)]
+
+
 class CtcSegmentArgs(C.Structure):
     """oe_ctc_segment_args (include/openeat_hip.h); filled by ops.ctc_segment."""
     _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
@@ -299,6 +305,8 @@ _SIGNATURES = {
     "oe_speed_perturb": (I, [P, L, P, P, I, I, P, L, P, P]),
     "oe_ctc_prefix_beam_workspace_bytes": (SZ, [I, I, I]),
     "oe_ctc_prefix_beam": (I, [C.POINTER(PrefixBeamArgs), P]),
+    "oe_ctc_prefix_beam_state_bytes": (SZ, [I, I, I]),
+    "oe_ctc_prefix_beam_chunk": (I, [C.POINTER(PrefixBeamChunk), P]),
     "oe_ctc_prefix_beam_host": (I, [P, P, I, I, I, P, P, P]),
     "oe_ctc_prefix_beam_host_batch": (I, [P, P, I, I, P, I, I, P, P, P, I]),
     "oe_ngram_score": (I, [C.POINTER(NgramModel), P, L, P, I, I, I, P, P, P, P]),
@@ -599,8 +607,23 @@ def prefix_beam(a: PrefixBeamArgs):
     check(lib().oe_ctc_prefix_beam(C.byref(a), stream()), "oe_ctc_prefix_beam")
 
 
+def prefix_beam_chunk(a: PrefixBeamArgs, state_in, state_out, stable_prefix, stable_frame, stable_len, out_frame=None, *, last=False,
+                      emit=True):
+    """oe_ctc_prefix_beam_chunk on the current stream: one chunk of the resumable search.  a: the chunk's oe_prefix_beam_args
+    (prefix_beam_args); state_in / state_out: uint8 tensors of oe_ctc_prefix_beam_state_bytes or None; the stable buffers and
+    out_frame: int32 tensors.  Nothing of the structs has to outlive the call."""
+    dp = lambda t: None if t is None else t.data_ptr()
+    c = PrefixBeamChunk()
+    c.search = C.pointer(a)
+    c.state_in, c.state_out, c.last, c.emit = dp(state_in), dp(state_out), int(bool(last)), int(bool(emit))
+    c.stable_prefix, c.stable_frame, c.stable_len, c.out_frame = dp(stable_prefix), dp(stable_frame), dp(stable_len), dp(out_frame)
+    check(lib().oe_ctc_prefix_beam_chunk(C.byref(c), stream()), "oe_ctc_prefix_beam_chunk")
+
+
 def check_prefix_beam_status(bad, name: str = "oe_ctc_prefix_beam"):
     """bad: the status word of a device prefix search, read after the stream has drained."""
+    if int(bad) == 2:
+        raise RuntimeError(f"{name}: the state was made by another search (beam, max_len, batch or variant differ)")
     if int(bad):
         raise RuntimeError(f"{name}: a prefix exceeded max_len")
 

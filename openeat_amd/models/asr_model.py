@@ -386,6 +386,119 @@ class ASRModel(torch.nn.Module):
         return out
 
     @torch.no_grad()
+    def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],
+                          margin: int = 16):
+        """The per-frame top-`beam_size` CTC log-probabilities of whole recordings, window by window: a generator over
+        utils.segment.window_plan that yields, for k = 0, 1, ..., (top_p (B, window, beam) float32, top_i (B, window, beam)
+        int64, lens (B) int32): the kept frames of the k-th window of every recording, lens[b] of them (0 for a recording that
+        has ended).  Only the k-th windows are encoded, as one batch, and only their kept frames' top-k rows are kept: the
+        (T', V) logits of a recording never exist.  window None: one window holds the longest recording."""
+        from openeat_amd.utils.segment import encoder_frames, window_plan
+        embed = self.encoder.embed
+        rate, rc = embed.subsampling_rate, embed.right_context
+        n_feats = [int(n) for n in features_length.tolist()]
+        n_enc = [encoder_frames(n, rate, rc) for n in n_feats]
+        window = max(n_enc + [1]) if window is None else min(int(window), max(n_enc + [1]))
+        plans = [window_plan(n, window, margin, rate, rc) for n in n_feats]
+        B, dev = len(n_feats), features.device
+        for k in range(max(len(p) for p in plans)):
+            live = [b for b in range(B) if k < len(plans[b])]
+            flen = torch.tensor([plans[b][k][1] - plans[b][k][0] for b in live], dtype=features_length.dtype, device=dev)
+            batch = features.new_zeros(len(live), int(flen.max()), features.shape[2])
+            for w, b in enumerate(live):
+                f0, f1 = plans[b][k][:2]
+                batch[w, : f1 - f0] = features[b, f0:f1]
+            encoder_out, _, _ = self._encode(batch, flen)
+            lg = self.ctc.logits(encoder_out)
+            kept = lg.new_zeros(B, window, lg.shape[2])
+            lens = [0] * B
+            for w, b in enumerate(live):
+                _, _, q0, q1, _ = plans[b][k]
+                kept[b, : q1 - q0] = lg[w, q0:q1]
+                lens[b] = q1 - q0
+            top_p, top_i = ops.topk_rows(kept, beam_size, log_softmax=True)
+            yield top_p, top_i, torch.tensor(lens, dtype=torch.int32).to(dev)
+
+    @torch.no_grad()
+    def transcribe_long(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int = 10, window: Optional[int] = 512,
+                        margin: int = 16, lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0, context=None,
+                        with_times: bool = False, frame_shift_ms: float = 10, on_partial=None, overlap: bool = False):
+        """Long-form transcription, the counterpart of ctc_segment (the reference has none; semantics in include/openeat_hip.h,
+        oe_ctc_prefix_beam_chunk): ctc_topk_windowed feeds a resumable CTC prefix beam search (utils.stream_search), plain or
+        with lm (an NgramLM) and / or context (a ContextGraph) as ctc_lm_beam_search / ctc_context_beam_search take them, so
+        neither the logits nor the back-pointers of a whole recording exist.  on_partial(b, tokens, frames) is called whenever
+        recording b's stable prefix - the tokens every live prefix shares, final from then on - has grown, with all of it.
+        overlap: window k+1 is encoded on a side stream while chunk k is searched.  -> per recording {"tokens", "frames" (the
+        encoder frame at which each token entered the beam; with_times "times", the (start_s, end_s) of that frame by
+        utils.align.frame_times), "score" (total), "ctc", "lm", "bias"} of the best hypothesis.  Needs the device beam and
+        beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
+        from openeat_amd import hip
+        from openeat_amd.utils.segment import encoder_frames
+        from openeat_amd.utils.stream_search import PrefixBeamStream
+        if lm is not None:
+            _require_fused_beam(lm, beam_size)
+        if context is not None:
+            _require_context_beam(context, beam_size)
+        if not DEVICE_BEAM:
+            raise ValueError("transcribe_long runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
+        if not 1 <= beam_size <= 16:
+            raise ValueError(f"transcribe_long supports beam sizes 1..16 (got {beam_size})")
+        B = features.shape[0]
+        assert B == features_length.shape[0]
+        embed = self.encoder.embed
+        rate = embed.subsampling_rate
+        max_len = max(max(encoder_frames(int(n), rate, embed.right_context) for n in features_length.tolist()), 1)
+        search = PrefixBeamStream(B, beam_size, max_len, features.device, lm, context, lm_weight if lm is not None else 0.0,
+                                  length_bonus if (lm is not None or context is not None) else 0.0)
+        windows = self.ctc_topk_windowed(features, features_length, beam_size, window, margin)
+        main = torch.cuda.current_stream(features.device)
+        side = torch.cuda.Stream(features.device) if overlap else None
+
+        def fetch():
+            """The next window's top-k, or None behind the last; with overlap it is produced on the side stream."""
+            if side is None:
+                return next(windows, None)
+            side.wait_stream(main)                                 # the features, and the buffers the last search has let go of
+            with torch.cuda.stream(side):
+                got = next(windows, None)
+            return got
+
+        seen = [0] * B
+        chunk = fetch()
+        if chunk is None:
+            raise ValueError("transcribe_long: nothing to transcribe")
+        while chunk is not None:
+            if side is not None:
+                main.wait_stream(side)
+                for t in chunk:
+                    t.record_stream(main)
+            ahead = fetch()                                        # with overlap: runs beside the search below
+            out = search.push(*chunk, last=ahead is None, emit=False, raw=True)
+            if on_partial is not None and ahead is not None:
+                n = out["stable_len"].cpu().tolist()               # drains the stream: the price of a partial result
+                for b in range(B):
+                    if n[b] > seen[b]:
+                        seen[b] = n[b]
+                        on_partial(b, out["stable_prefix"][b, : n[b]].cpu().tolist(), out["stable_frame"][b, : n[b]].cpu().tolist())
+            chunk = ahead
+        hip.check_prefix_beam_status(out["status"][0], "transcribe_long")           # the read drains the stream
+        n = out["plen"][:, 0].cpu().tolist()
+        width = max(n + [1])
+        toks, frames = out["prefixes"][:, 0, :width].cpu().numpy(), out["frames"][:, 0, :width].cpu().numpy()
+        scores = [out[k][:, 0].cpu().tolist() for k in ("total", "ctc", "lm", "bias")]
+        res = []
+        for b in range(B):
+            fr = frames[b, : n[b]].tolist()
+            if on_partial is not None and n[b] > seen[b]:          # at the end the best hypothesis is all stable
+                on_partial(b, toks[b, : n[b]].tolist(), fr)
+            r = {"tokens": toks[b, : n[b]].tolist(), "frames": fr, "score": scores[0][b], "ctc": scores[1][b],
+                 "lm": scores[2][b] if lm is not None else 0.0, "bias": scores[3][b] if context is not None else 0.0}
+            if with_times:
+                r["times"] = [frame_times(f, f, rate, frame_shift_ms) for f in fr]
+            res.append(r)
+        return res
+
+    @torch.no_grad()
     def error_counts(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
                      targets_length: torch.Tensor, mode: str = "ctc_greedy_search", beam_size: int = 10,
                      nbest_oracle: bool = False, **decode_kwargs) -> dict:
