@@ -7,7 +7,9 @@ HIP stream.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import dataclasses
 import os
 from typing import Optional
 
@@ -637,32 +639,100 @@ def _nbest_lists(prefixes, plen, *scores):
             for b in range(B)]
 
 
-def _prefix_beam_device(name, top_logp, top_idx, lens, beam, n_scores, raw, lm=None, graph=None, **weights):
-    """What the three device prefix searches share (name: of the caller, for its messages): the argument check, the
-    allocations - workspace (status word zeroed), prefixes (B, beam, max_len) int32, lengths (B, beam) int32, n_scores x
-    (B, beam) float64 = score [, ctc, lm [, bias]] - and the launch -> the raw tuple or the lists, as the callers document."""
+SCORES = ("total", "ctc", "lm", "bias")                             # out_score, out_ctc, out_lm, out_bias of oe_prefix_beam_args
+# a one-shot search's device tensors: prefixes (B, beam, max_len) int32, plen (B, beam) int32, (B, beam) float64 scores, status word
+PrefixBeamResult = collections.namedtuple("PrefixBeamResult", ("prefixes", "plen") + SCORES + ("status",))
+
+
+@dataclasses.dataclass(frozen=True)
+class PrefixSearch:
+    """One device CTC prefix beam search (oe_ctc_prefix_beam; semantics in include/openeat_hip.h): the beam, the NgramLM and
+    the ContextGraph that take part (None: not) and the weights.  Numbers compare by value, lm and context by identity
+    (neither class defines __eq__), so a spec is a dict key under which its LM and graph stay alive."""
+    beam: int
+    lm: object = None
+    context: object = None
+    lm_weight: float = 0.0
+    length_bonus: float = 0.0
+    eos: bool = True
+    final: bool = True
+
+    @classmethod
+    def first_pass(cls, beam, lm, lm_weight, first_pass_lm, first_pass_lm_weight, length_bonus, context):
+        """The search behind attention_rescoring_batch's n-best lists: the LM only with first_pass_lm, an NgramLM and lm_weight
+        > 0, weighted first_pass_lm_weight (None: lm_weight); the graph always; weights only for what takes part."""
+        from openeat_amd.models.ngram_lm import NgramLM
+        if not (first_pass_lm and isinstance(lm, NgramLM) and lm_weight > 0):
+            lm, first_pass_lm_weight = None, 0.0
+        if lm is None and context is None:
+            return cls(beam)
+        return cls(beam, lm, context, float(lm_weight if first_pass_lm_weight is None else first_pass_lm_weight), float(length_bonus))
+
+    @property
+    def plain(self):
+        return self.lm is None and self.context is None
+
+    def validate(self, caller: str, device_beam: bool, require=()):
+        """The refusals of the model's entry points, ValueErrors in `caller`'s name: a field of `require` missing, a wrong type,
+        the host beam selected (device_beam: asr_model.DEVICE_BEAM at the time of the call), a beam outside 1..16."""
+        from openeat_amd.models.ngram_lm import NgramLM
+        from openeat_amd.utils.context_graph import ContextGraph as Graph
+        for field, cls in (("lm", NgramLM), ("context", Graph)):
+            got = getattr(self, field)
+            if not isinstance(got, cls) and (got is not None or field in require):
+                raise ValueError(f"{caller}: {field} must be of type {cls.__name__} (got {type(got).__name__})")
+        if not device_beam:
+            raise ValueError(f"{caller} runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
+        if not 1 <= self.beam <= 16:
+            raise ValueError(f"{caller} supports beam sizes 1..16 (got {self.beam})")
+
+    @property
+    def plan(self):
+        """The search's outputs among SCORES -> True: the kernel writes it; False: it is not passed (pb_prepare's null-pointer
+        rule in beam.hip) and the caller sees zeros.  Plain: the total alone, which is the ctc score too."""
+        if self.plain:
+            return dict(total=True)
+        return dict(total=True, ctc=True, lm=self.lm is not None, **({} if self.context is None else dict(bias=True)))
+
+    def bind(self, buf):
+        """buf: name -> tensor, the plan's names at least -> (the kernel's out_* arguments in SCORES' order, None where it
+        writes nothing; what the caller sees by name: ctc is the total in the plain search, None where there is no buffer)."""
+        seen = dict({k: buf.get(k) for k in SCORES}, ctc=buf["total" if self.plain else "ctc"])
+        return [buf[k] if self.plan.get(k) else None for k in SCORES], seen
+
+    def abi(self, device):
+        """prefix_beam_args' keywords: the oe_ngram_model / oe_context_graph with their tables on `device`, and the weights."""
+        return dict(lm=None if self.lm is None else ngram_model(self.lm, device),
+                    ctx=None if self.context is None else context_graph(self.context, device),
+                    lm_weight=self.lm_weight, length_bonus=self.length_bonus, eos=self.eos, final=self.final)
+
+
+def _prefix_beam_device(caller, top_logp, top_idx, lens, spec: PrefixSearch, raw) -> PrefixBeamResult:
+    """The one launcher of the one-shot device prefix searches (caller: for the messages): the argument check, the allocations
+    - workspace (status word zeroed), prefixes, lengths, one score tensor per name of spec.plan (an unwritten one zeroed) -
+    and the launch.  raw: nothing is read back, the caller checks `status` after its own wait; else it is checked here."""
     if not (top_logp.is_cuda and top_idx.is_cuda and top_logp.dtype == torch.float32 and top_idx.dtype == torch.int64):
-        raise TypeError(f"{name}: float32 / int64 CUDA tensors required")
+        raise TypeError(f"{caller}: float32 / int64 CUDA tensors required")
     top_logp, top_idx = top_logp.contiguous(), top_idx.contiguous()
     B, T = top_logp.shape[0], top_logp.shape[1]
     ml = max(T, 1)
     dev = top_logp.device
-    ws = torch.empty(lib().oe_ctc_prefix_beam_workspace_bytes(B, T, beam) // 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib().oe_ctc_prefix_beam_workspace_bytes(B, T, spec.beam) // 4, dtype=torch.int32, device=dev)
     ws[-1:].zero_()
-    prefixes = torch.zeros(B, beam, ml, dtype=torch.int32, device=dev)
-    plen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    scores = [torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(n_scores)]
-    outs = list(scores)
-    if graph is not None and lm is None:                           # out_lm is not written without an LM: the caller gets zeros
-        scores[2].zero_()
-        outs[2] = None
-    prefix_beam(prefix_beam_args(top_logp, top_idx, lens, beam, ml, ws, prefixes, plen, *outs,
-                                 lm=None if lm is None else ngram_model(lm, dev),
-                                 ctx=None if graph is None else context_graph(graph, dev), **weights))
-    if raw:
-        return (prefixes, plen, *scores, ws[-1:])
-    check_prefix_beam_status(ws[-1], name)                         # the read drains the stream
-    return _nbest_lists(prefixes, plen, *scores)
+    prefixes = torch.zeros(B, spec.beam, ml, dtype=torch.int32, device=dev)
+    plen = torch.empty(B, spec.beam, dtype=torch.int32, device=dev)
+    buf = {k: (torch.empty if written else torch.zeros)(B, spec.beam, dtype=torch.float64, device=dev) for k, written in spec.plan.items()}
+    outs, seen = spec.bind(buf)
+    prefix_beam(prefix_beam_args(top_logp, top_idx, lens, spec.beam, ml, ws, prefixes, plen, *outs, **spec.abi(dev)))
+    if not raw:
+        check_prefix_beam_status(ws[-1], caller)                   # the read drains the stream
+    return PrefixBeamResult(prefixes, plen, status=ws[-1:], **seen)
+
+
+def _shaped(r: PrefixBeamResult, raw, *names):
+    """What the public searches document: raw, the tuple (prefixes, plen, *the named scores, status); else the n-best lists."""
+    scores = [getattr(r, k) for k in names]
+    return (r.prefixes, r.plen, *scores, r.status) if raw else _nbest_lists(r.prefixes, r.plen, *scores)
 
 
 def ctc_prefix_beam_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, raw: bool = False):
@@ -671,7 +741,7 @@ def ctc_prefix_beam_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: 
     utterance; one device-to-host copy of the n-best lists.  raw=True: no copy at all - the device tensors
     (prefixes (B, beam, T) int32, lengths (B, beam) int32 with -1 for missing entries, scores (B, beam) float64) and a
     status word tensor the caller checks after its own synchronisation."""
-    return _prefix_beam_device("ctc_prefix_beam_device", top_logp, top_idx, lens, beam, 1, raw)
+    return _shaped(_prefix_beam_device("ctc_prefix_beam_device", top_logp, top_idx, lens, PrefixSearch(beam), raw), raw, "total")
 
 
 def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, lm,
@@ -681,8 +751,8 @@ def ctc_prefix_beam_lm_device(top_logp: torch.Tensor, top_idx: torch.Tensor, len
     [(prefix tuple, total, ctc, lm)] sorted by total.  raw=True: no copy at all - the device tensors (prefixes (B, beam, T)
     int32, lengths (B, beam) int32 with -1 for missing entries, total / ctc / lm (B, beam) float64, -inf where missing) and
     the status word tensor the caller checks after its own synchronisation."""
-    return _prefix_beam_device("ctc_prefix_beam_lm_device", top_logp, top_idx, lens, beam, 3, raw, lm, lm_weight=lm_weight,
-                               length_bonus=length_bonus, eos=eos)
+    spec = PrefixSearch(beam, lm, None, lm_weight, length_bonus, eos)
+    return _shaped(_prefix_beam_device("ctc_prefix_beam_lm_device", top_logp, top_idx, lens, spec, raw), raw, "total", "ctc", "lm")
 
 
 def ctc_prefix_beam_ctx_device(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int, graph, lm=None,
@@ -694,8 +764,8 @@ def ctc_prefix_beam_ctx_device(top_logp: torch.Tensor, top_idx: torch.Tensor, le
     lm = 0.0 when no LM is given.  final: the pending partial credit is dropped at the end of the utterance.  raw=True: no
     copy at all - the device tensors (prefixes, lengths, total / ctc / lm / bias (B, beam) float64, -inf where missing; lm
     all zero without an LM) and the status word tensor the caller checks after its own synchronisation."""
-    return _prefix_beam_device("ctc_prefix_beam_ctx_device", top_logp, top_idx, lens, beam, 4, raw, lm, graph, lm_weight=lm_weight,
-                               length_bonus=length_bonus, eos=eos, final=final)
+    spec = PrefixSearch(beam, lm, graph, lm_weight, length_bonus, eos, final)
+    return _shaped(_prefix_beam_device("ctc_prefix_beam_ctx_device", top_logp, top_idx, lens, spec, raw), raw, *SCORES)
 
 
 def ctc_prefix_beam_host_batch(top_logp: torch.Tensor, top_idx: torch.Tensor, lens, beam: int, n_threads: int = 0):

@@ -10,7 +10,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from openeat_amd import ops
+from openeat_amd import hip, ops
 from openeat_amd import planes as _planes
 from openeat_amd.models.ngram_lm import NgramLM
 from openeat_amd.modules.cmvn import GlobalCMVN
@@ -33,37 +33,21 @@ EDIT_DISTANCE_MAX = 1023                                                     # o
 ATT_INPUTS_KERNEL = os.environ.get("OE_ATT_INPUTS_KERNEL", "1") != "0"      # decoder token bookkeeping as one launch (fixed widths)
 
 
-def _require_fused_beam(lm, beam_size):
-    """The LM-fused prefix search exists on the device only (beam.hip): an NgramLM, the device beam, beam <= 16."""
-    if not isinstance(lm, NgramLM):
-        raise ValueError(f"the LM-fused CTC beam search needs an NgramLM (got {type(lm).__name__})")
-    if not DEVICE_BEAM:
-        raise ValueError("the LM-fused CTC beam search runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
-    if not 1 <= beam_size <= 16:
-        raise ValueError(f"the LM-fused CTC beam search supports beam sizes 1..16 (got {beam_size})")
-
-
-def _require_context_beam(context, beam_size):
-    """The hotword-biased prefix search exists on the device only (beam.hip): a ContextGraph, the device beam, beam <= 16."""
-    from openeat_amd.utils.context_graph import ContextGraph
-    if not isinstance(context, ContextGraph):
-        raise ValueError(f"the hotword-biased CTC beam search needs a ContextGraph (got {type(context).__name__})")
-    if not DEVICE_BEAM:
-        raise ValueError("the hotword-biased CTC beam search runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
-    if not 1 <= beam_size <= 16:
-        raise ValueError(f"the hotword-biased CTC beam search supports beam sizes 1..16 (got {beam_size})")
+def _device_beam(beam_size):
+    """Whether the plain prefix recursion of this beam runs on the device (DEVICE_BEAM is read at the time of the call)."""
+    return DEVICE_BEAM and beam_size <= 16
 
 
 def _graph_call(cache, key, fn, args):
     """fn(*args) through a per-key HIP graph: first call eager (lazy state must exist before a capture) and captured for
     the next time, later calls copy the arguments into the capture's static inputs and replay.  Outputs are the capture's
-    own tensors (valid until the next replay of the same key).  A key whose capture failed stays eager."""
+    own tensors (valid until the next replay of the same key).  A key whose capture failed stays eager.  None stays None."""
     rec = cache.get(key, False)
     if rec is None:
         return fn(*args)
     if rec is False:
         out = fn(*args)                                            # the real result of this call
-        static = tuple(a.clone() for a in args)
+        static = tuple(None if a is None else a.clone() for a in args)
         g = torch.cuda.CUDAGraph()
         try:
             torch.cuda.synchronize()
@@ -82,7 +66,8 @@ def _graph_call(cache, key, fn, args):
         return out
     g, static, sout = rec
     for s_, a in zip(static, args):
-        s_.copy_(a)
+        if a is not None:
+            s_.copy_(a)
     g.replay()
     return sout
 
@@ -188,7 +173,6 @@ class ASRModel(torch.nn.Module):
         if ATT_INPUTS_KERNEL and common.STATIC_SHAPES and ys_pad.is_cuda and ys_pad.dtype == torch.int32 and ys_pad_lens.dtype == torch.int32 \
                 and ys_pad.dim() == 2 and ys_pad.shape[1] <= 8000:
             # fixed width (a captured step): one launch instead of ~70 index-arithmetic launches
-            from openeat_amd import hip
             B, L = ys_pad.shape
             W = L + 1
             rev = self.reverse_weight > 0
@@ -254,16 +238,38 @@ class ASRModel(torch.nn.Module):
         return loss_att, r_loss, torch.true_divide(n_ok, n_valid)
 
     # ----------------------------------------------------------------- decode --
-    def ctc_greedy_search(self, features: torch.Tensor, features_length: torch.Tensor) -> List[List[int]]:
-        """asr_model.py:297-326: argmax / eos-fill / collapse all on device; one D2H copy of the result."""
-        assert features.shape[0] == features_length.shape[0]
+    def _ctc_greedy(self, features, features_length):
+        """asr_model.py:297-326 on the device: argmax / eos-fill / collapse -> tokens (B, T') and their counts (B)."""
         encoder_out, encoder_mask, _ = self._encode(features, features_length)
         lens = encoder_mask.squeeze(1).sum(1)
         logits = self.ctc.logits(encoder_out)
         B, T, V = logits.shape
-        toks, n = ops.ctc_greedy(logits, V, B, T, V, lens, self.eos)
+        return ops.ctc_greedy(logits, V, B, T, V, lens, self.eos)
+
+    def _ctc_topk(self, features, features_length, beam_size):
+        """What every prefix search starts from: one encoder pass, the valid encoder frames (B) int32 and the fused log-softmax
+        top-k of the CTC logits -> encoder_out, encoder_mask, lens, top_p (B, T', beam) float32, top_i (B, T', beam) int64."""
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1).to(torch.int32)
+        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
+        return encoder_out, encoder_mask, lens, top_p, top_i
+
+    def _span_logits(self, features, features_length, spans):
+        """spans: [(recording, f0, f1)], feature frames f0..f1 of a recording -> the CTC logits (len(spans), T', V) of the spans
+        encoded as ONE batch, zero-padded to the longest."""
+        flen = torch.tensor([f1 - f0 for _, f0, f1 in spans], dtype=features_length.dtype, device=features.device)
+        batch = features.new_zeros(len(spans), int(flen.max()), features.shape[2])
+        for w, (b, f0, f1) in enumerate(spans):
+            batch[w, : f1 - f0] = features[b, f0:f1]
+        encoder_out, _, _ = self._encode(batch, flen)
+        return self.ctc.logits(encoder_out)
+
+    def ctc_greedy_search(self, features: torch.Tensor, features_length: torch.Tensor) -> List[List[int]]:
+        """asr_model.py:297-326: argmax / eos-fill / collapse all on device; one D2H copy of the result."""
+        assert features.shape[0] == features_length.shape[0]
+        toks, n = self._ctc_greedy(features, features_length)
         toks, n = toks.cpu(), n.cpu()
-        return [toks[b, : int(n[b])].tolist() for b in range(B)]
+        return [toks[b, : int(n[b])].tolist() for b in range(len(n))]
 
     @torch.no_grad()
     def ctc_align(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
@@ -319,12 +325,7 @@ class ASRModel(torch.nn.Module):
         out = None
         for b, n in enumerate(n_feats):
             plan = window_plan(n, window, margin, rate, rc)
-            flen = torch.tensor([f1 - f0 for f0, f1, _, _, _ in plan], dtype=features_length.dtype, device=features.device)
-            batch = features.new_zeros(len(plan), int(flen.max()), features.shape[2])
-            for w, (f0, f1, _, _, _) in enumerate(plan):
-                batch[w, : f1 - f0] = features[b, f0:f1]
-            encoder_out, _, _ = self._encode(batch, flen)
-            lg = self.ctc.logits(encoder_out)
+            lg = self._span_logits(features, features_length, [(b, f0, f1) for f0, f1, _, _, _ in plan])
             if out is None:
                 out = lg.new_zeros(len(n_feats), max(n_enc), lg.shape[2])
             for w, (_, _, q0, q1, o0) in enumerate(plan):
@@ -403,13 +404,7 @@ class ASRModel(torch.nn.Module):
         B, dev = len(n_feats), features.device
         for k in range(max(len(p) for p in plans)):
             live = [b for b in range(B) if k < len(plans[b])]
-            flen = torch.tensor([plans[b][k][1] - plans[b][k][0] for b in live], dtype=features_length.dtype, device=dev)
-            batch = features.new_zeros(len(live), int(flen.max()), features.shape[2])
-            for w, b in enumerate(live):
-                f0, f1 = plans[b][k][:2]
-                batch[w, : f1 - f0] = features[b, f0:f1]
-            encoder_out, _, _ = self._encode(batch, flen)
-            lg = self.ctc.logits(encoder_out)
+            lg = self._span_logits(features, features_length, [(b, *plans[b][k][:2]) for b in live])
             kept = lg.new_zeros(B, window, lg.shape[2])
             lens = [0] * B
             for w, b in enumerate(live):
@@ -432,24 +427,18 @@ class ASRModel(torch.nn.Module):
         encoder frame at which each token entered the beam; with_times "times", the (start_s, end_s) of that frame by
         utils.align.frame_times), "score" (total), "ctc", "lm", "bias"} of the best hypothesis.  Needs the device beam and
         beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
-        from openeat_amd import hip
         from openeat_amd.utils.segment import encoder_frames
         from openeat_amd.utils.stream_search import PrefixBeamStream
-        if lm is not None:
-            _require_fused_beam(lm, beam_size)
-        if context is not None:
-            _require_context_beam(context, beam_size)
-        if not DEVICE_BEAM:
-            raise ValueError("transcribe_long runs on the device only (OE_DEVICE_BEAM=0 selects the host recursion)")
-        if not 1 <= beam_size <= 16:
-            raise ValueError(f"transcribe_long supports beam sizes 1..16 (got {beam_size})")
+        # a weight without the part it weighs is dropped: the plain search takes none
+        spec = hip.PrefixSearch(beam_size, lm, context, lm_weight if lm is not None else 0.0,
+                                length_bonus if (lm is not None or context is not None) else 0.0)
+        spec.validate("transcribe_long", DEVICE_BEAM)
         B = features.shape[0]
         assert B == features_length.shape[0]
         embed = self.encoder.embed
         rate = embed.subsampling_rate
         max_len = max(max(encoder_frames(int(n), rate, embed.right_context) for n in features_length.tolist()), 1)
-        search = PrefixBeamStream(B, beam_size, max_len, features.device, lm, context, lm_weight if lm is not None else 0.0,
-                                  length_bonus if (lm is not None or context is not None) else 0.0)
+        search = PrefixBeamStream.of(spec, B, max_len, features.device)
         windows = self.ctc_topk_windowed(features, features_length, beam_size, window, margin)
         main = torch.cuda.current_stream(features.device)
         side = torch.cuda.Stream(features.device) if overlap else None
@@ -485,14 +474,14 @@ class ASRModel(torch.nn.Module):
         n = out["plen"][:, 0].cpu().tolist()
         width = max(n + [1])
         toks, frames = out["prefixes"][:, 0, :width].cpu().numpy(), out["frames"][:, 0, :width].cpu().numpy()
-        scores = [out[k][:, 0].cpu().tolist() for k in ("total", "ctc", "lm", "bias")]
+        scores = [out[k][:, 0].cpu().tolist() for k in hip.SCORES]         # (a part the search has not: zeros)
         res = []
         for b in range(B):
             fr = frames[b, : n[b]].tolist()
             if on_partial is not None and n[b] > seen[b]:          # at the end the best hypothesis is all stable
                 on_partial(b, toks[b, : n[b]].tolist(), fr)
-            r = {"tokens": toks[b, : n[b]].tolist(), "frames": fr, "score": scores[0][b], "ctc": scores[1][b],
-                 "lm": scores[2][b] if lm is not None else 0.0, "bias": scores[3][b] if context is not None else 0.0}
+            r = {"tokens": toks[b, : n[b]].tolist(), "frames": fr, "score": scores[0][b], "ctc": scores[1][b], "lm": scores[2][b],
+                 "bias": scores[3][b]}
             if with_times:
                 r["times"] = [frame_times(f, f, rate, frame_shift_ms) for f in fr]
             res.append(r)
@@ -516,15 +505,11 @@ class ASRModel(torch.nn.Module):
         if mode == "ctc_greedy_search":
             if nbest_oracle:
                 raise ValueError("error_counts: ctc_greedy_search has no n-best list")
-            encoder_out, encoder_mask, _ = self._encode(features, features_length)
-            lens = encoder_mask.squeeze(1).sum(1)
-            logits = self.ctc.logits(encoder_out)
-            B, T, V = logits.shape
-            toks, n = ops.ctc_greedy(logits, V, B, T, V, lens, self.eos)
+            toks, n = self._ctc_greedy(features, features_length)
             return {"counts": ops.edit_distance(targets, targets_length, toks[:, :EDIT_DISTANCE_MAX], n)}
         if mode != "attention_rescoring":
             raise ValueError(f"error_counts: unknown mode {mode!r}")
-        if nbest_oracle and not (DEVICE_BEAM and beam_size <= 16):
+        if nbest_oracle and not _device_beam(beam_size):
             raise NotImplementedError("error_counts: nbest_oracle needs the device beam (OE_DEVICE_BEAM=1, beam_size <= 16)")
         hyps = self.attention_rescoring_batch(features, features_length, beam_size, **decode_kwargs)
         hl = [len(h) for h in hyps]
@@ -533,7 +518,7 @@ class ASRModel(torch.nn.Module):
             pad[b, : hl[b]] = torch.tensor(h, dtype=torch.int32)
         out = {"counts": ops.edit_distance(targets, targets_length, pad.to(device), torch.tensor(hl, dtype=torch.int32).to(device))}
         if nbest_oracle:
-            _, _, pre, plen, _, _ = self._rescore_stage1(features, features_length, beam_size)
+            _, _, pre, plen, _, _, _ = self._rescore_stage1(features, features_length, hip.PrefixSearch(beam_size))
             out["oracle_counts"], out["oracle_index"] = oracle_of(
                 ops.edit_distance(targets, targets_length, pre[:, :EDIT_DISTANCE_MAX], plen, group=beam_size), beam_size)
         return out
@@ -543,12 +528,10 @@ class ASRModel(torch.nn.Module):
         recursion in native host code (oe_ctc_prefix_beam_host: same ordering and float64 arithmetic)."""
         assert features.shape[0] == features_length.shape[0]
         assert features.shape[0] == 1
-        encoder_out, _, _ = self._encode(features, features_length)
-        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out).squeeze(0), beam_size, log_softmax=True)
-        from openeat_amd import hip
-        if DEVICE_BEAM and beam_size <= 16:
-            return hip.ctc_prefix_beam_device(top_p.unsqueeze(0), top_i.unsqueeze(0), None, beam_size)[0], encoder_out
-        return hip.ctc_prefix_beam_host(top_p.cpu(), top_i.cpu(), beam_size), encoder_out
+        encoder_out, _, _, top_p, top_i = self._ctc_topk(features, features_length, beam_size)
+        if _device_beam(beam_size):                                # (the reference searches every frame of its one utterance)
+            return hip.ctc_prefix_beam_device(top_p, top_i, None, beam_size)[0], encoder_out
+        return hip.ctc_prefix_beam_host(top_p[0].cpu(), top_i[0].cpu(), beam_size), encoder_out
 
     def ctc_prefix_beam_search(self, features, features_length, beam_size: int) -> List[int]:
         hyps, _ = self._ctc_prefix_beam_search(features, features_length, beam_size)
@@ -561,13 +544,9 @@ class ASRModel(torch.nn.Module):
         include/openeat_hip.h): prefixes are pruned every frame by log_add(pb, pnb) + lm_weight * LM + length_bonus * len.
         -> per utterance [(prefix tuple, total, ctc, lm)] sorted by total.  Needs an NgramLM, the device beam and
         beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
-        from openeat_amd import hip
-        _require_fused_beam(lm, beam_size)
-        assert features.shape[0] == features_length.shape[0]
-        encoder_out, encoder_mask, _ = self._encode(features, features_length)
-        lens = encoder_mask.squeeze(1).sum(1)
-        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
-        return hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, lm, lm_weight, length_bonus, eos)
+        spec = hip.PrefixSearch(beam_size, lm, None, lm_weight, length_bonus, eos)
+        spec.validate("ctc_lm_beam_search", DEVICE_BEAM, require=("lm",))
+        return hip._shaped(self._prefix_beam_search("ctc_lm_beam_search", features, features_length, spec), False, "total", "ctc", "lm")
 
     @torch.no_grad()
     def ctc_context_beam_search(self, features, features_length, beam_size: int, context, lm=None, lm_weight: float = 0.0,
@@ -577,15 +556,15 @@ class ASRModel(torch.nn.Module):
         score `context`, a ContextGraph, gives the hotwords a prefix holds, plus a per-token credit while one is half spoken;
         at the end of the utterance the pending credit is dropped.  -> per utterance [(prefix tuple, total, ctc, lm, bias)]
         sorted by total.  Needs the device beam and beam_size <= 16 (ValueError otherwise: there is no host implementation)."""
-        from openeat_amd import hip
-        _require_context_beam(context, beam_size)
-        if lm is not None:
-            _require_fused_beam(lm, beam_size)
+        spec = hip.PrefixSearch(beam_size, lm, context, lm_weight, length_bonus, eos)
+        spec.validate("ctc_context_beam_search", DEVICE_BEAM, require=("context",))
+        return hip._shaped(self._prefix_beam_search("ctc_context_beam_search", features, features_length, spec), False, *hip.SCORES)
+
+    def _prefix_beam_search(self, caller, features, features_length, spec):
+        """_ctc_topk and on it the device prefix search `spec`, a hip.PrefixSearch -> the hip.PrefixBeamResult, status checked."""
         assert features.shape[0] == features_length.shape[0]
-        encoder_out, encoder_mask, _ = self._encode(features, features_length)
-        lens = encoder_mask.squeeze(1).sum(1)
-        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
-        return hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens.to(torch.int32), beam_size, context, lm, lm_weight, length_bonus, eos)
+        _, _, lens, top_p, top_i = self._ctc_topk(features, features_length, spec.beam)
+        return hip._prefix_beam_device(caller, top_p, top_i, lens, spec, False)
 
     def attention_rescoring(self, features, features_length, beam_size: int, ctc_weight: float = 0.0,
                             reverse_weight: float = 0.0, lm: Optional[torch.nn.Module] = None, lm_weight: float = 0,
@@ -657,37 +636,28 @@ class ASRModel(torch.nn.Module):
         context: a ContextGraph of hotwords - the n-best lists come from the biased search (ctc_context_beam_search's kernel,
         with the LM only under the first_pass_lm rule, and with length_bonus), and every hypothesis' final bias is added to
         its mixed score, since nothing else in the rescoring knows about hotwords.  Device beam only."""
-        from openeat_amd import hip
         device = features.device
         B = features.shape[0]
         R = B * beam_size
         if reverse_weight > 0 and self.decoder.r_num_blocks == 0:
             raise IndexError("reverse_weight > 0 needs r_decoder_num_blocks > 0 (as in the reference)")
-        on_device = DEVICE_BEAM and beam_size <= 16
         graphs = DECODE_GRAPHS if use_graphs is None else bool(use_graphs)
-        fuse = None
-        if first_pass_lm and isinstance(lm, NgramLM) and lm_weight > 0:
-            _require_fused_beam(lm, beam_size)
-            fuse = (lm, float(lm_weight if first_pass_lm_weight is None else first_pass_lm_weight), float(length_bonus))
-        if context is not None:
-            _require_context_beam(context, beam_size)
-            if fuse is None:                                       # no LM in the first pass: the length bonus alone
-                fuse = (None, 0.0, float(length_bonus))
-            fuse = fuse + (context,)
+        spec = hip.PrefixSearch.first_pass(beam_size, lm, lm_weight, first_pass_lm, first_pass_lm_weight, length_bonus, context)
+        if not spec.plain:                                         # (the plain search alone has a host implementation)
+            spec.validate("attention_rescoring_batch", DEVICE_BEAM)
+        on_device = _device_beam(beam_size)
         if on_device and graphs:
-            return self._rescoring_batch_graphs(features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight, fuse)
+            return self._rescoring_batch_graphs(features, features_length, spec, ctc_weight, reverse_weight, lm, lm_weight)
         if on_device:
-            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, *bias = self._rescore_stage1(features, features_length, beam_size, fuse)
+            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, bias = self._rescore_stage1(features, features_length, spec)
             Lm = max(int(plen.max()), 1)                           # the one host sync of the n-best stage
             hip.check_prefix_beam_status(bad)
             toks, n, mean_len = self._rescore_stage2(encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight,
-                                                     reverse_weight, lm, lm_weight, *bias)
+                                                     reverse_weight, lm, lm_weight, bias)
             self.last_nbest_mean_len = float(mean_len)
             toks, n = toks.cpu(), n.cpu().tolist()
             return [toks[b, : n[b]].tolist() for b in range(B)]
-        encoder_out, encoder_mask, _ = self._encode(features, features_length)
-        lens = encoder_mask.squeeze(1).sum(1)
-        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
+        encoder_out, encoder_mask, lens, top_p, top_i = self._ctc_topk(features, features_length, beam_size)
         nbest = hip.ctc_prefix_beam_host_batch(top_p.cpu(), top_i.cpu(), lens.cpu().tolist(), beam_size)
         for b in range(B):                                         # a very short utterance can yield fewer than `beam` prefixes
             while len(nbest[b]) < beam_size:
@@ -706,28 +676,15 @@ class ASRModel(torch.nn.Module):
         return [list(nbest[b][best[b]][0]) for b in range(B)]
 
     # ---- the pieces of the batched rescoring (each of fixed shape given (B, T) resp. (B, T', L): capturable) --------------
-    def _rescore_stage1(self, features, features_length, beam_size, fuse=None):
-        """Encoder, CTC projection, fused log-softmax top-k, prefix recursion - all on the device, no host sync.
-        Returns encoder_out, encoder_mask, prefixes (R, T') int32, lengths (R) int32 (-1: the slot does not exist), CTC
-        scores (R) float64, status word.  fuse = (NgramLM, weight, length bonus): the LM-fused recursion picks the prefixes;
-        fuse = (NgramLM or None, weight, length bonus, ContextGraph): the hotword-biased one does, and the hypotheses' final
-        bias (R) float64 is returned as a seventh value."""
-        from openeat_amd import hip
-        encoder_out, encoder_mask, _ = self._encode(features, features_length)
-        lens = encoder_mask.squeeze(1).sum(1)
-        top_p, top_i = ops.topk_rows(self.ctc.logits(encoder_out), beam_size, log_softmax=True)
-        if fuse is not None and len(fuse) == 4:
-            pre, plen, _, ctc_scores, _, bias, bad = hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens.to(torch.int32), beam_size, fuse[3],
-                                                                                   fuse[0], fuse[1], fuse[2], eos=True, final=True, raw=True)
-            R = pre.shape[0] * beam_size
-            return encoder_out, encoder_mask, pre.view(R, -1), plen.view(R), ctc_scores.view(R), bad, bias.view(R)
-        if fuse is not None:
-            pre, plen, _, ctc_scores, _, bad = hip.ctc_prefix_beam_lm_device(top_p, top_i, lens.to(torch.int32), beam_size, fuse[0],
-                                                                             fuse[1], fuse[2], eos=True, raw=True)
-        else:
-            pre, plen, ctc_scores, bad = hip.ctc_prefix_beam_device(top_p, top_i, lens.to(torch.int32), beam_size, raw=True)
-        R = pre.shape[0] * beam_size
-        return encoder_out, encoder_mask, pre.view(R, -1), plen.view(R), ctc_scores.view(R), bad
+    def _rescore_stage1(self, features, features_length, spec):
+        """Encoder, CTC projection, fused log-softmax top-k and the prefix recursion `spec` (a hip.PrefixSearch) - all on the
+        device, no host sync.  Returns encoder_out, encoder_mask, prefixes (R, T') int32, lengths (R) int32 (-1: the slot does
+        not exist), CTC scores (R) float64, status word, the hypotheses' final bias (R) float64 (None without a graph)."""
+        encoder_out, encoder_mask, lens, top_p, top_i = self._ctc_topk(features, features_length, spec.beam)
+        r = hip._prefix_beam_device("attention_rescoring_batch", top_p, top_i, lens, spec, True)
+        R = r.plen.numel()
+        return (encoder_out, encoder_mask, r.prefixes.view(R, -1), r.plen.view(R), r.ctc.view(R), r.status,
+                None if r.bias is None else r.bias.view(R))
 
     def _rescore_stage2(self, encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight, reverse_weight, lm, lm_weight,
                         bias=None):
@@ -787,35 +744,29 @@ class ASRModel(torch.nn.Module):
         score = score.masked_fill(missing, -float("inf"))         # (0 * -inf above would be nan: the slot is out whatever the weights)
         return score.view(B, beam_size).argmax(1)
 
-    def _rescoring_batch_graphs(self, features, features_length, beam_size, ctc_weight, reverse_weight, lm, lm_weight, fuse=None):
+    def _rescoring_batch_graphs(self, features, features_length, spec, ctc_weight, reverse_weight, lm, lm_weight):
         """The same two stages replayed from HIP graphs (decode is launch-bound: ~1500 small launches for 64 utterances):
-        stage 1 keyed by the feature shape, stage 2 by the n-best length rounded up to a multiple of 16; between them the one
-        host read of the longest hypothesis.  A shape is run eagerly the first time it is seen and captured for the next;
-        a stage that cannot be captured keeps running eagerly.  At most DECODE_GRAPH_SLOTS graphs per stage are kept."""
-        from openeat_amd import hip
+        stage 1 keyed by the feature shape and the search, stage 2 by the n-best length rounded up to a multiple of 16; between
+        them the one host read of the longest hypothesis.  A shape is run eagerly the first time it is seen and captured for the
+        next; a stage that cannot be captured keeps running eagerly.  At most DECODE_GRAPH_SLOTS graphs per stage are kept.
+        The keys hold the LM and the context graph themselves (by identity): the tables a capture points at live as long as it."""
         from openeat_amd.utils import common
-        B = features.shape[0]
+        B, beam_size = features.shape[0], spec.beam
         cache = self.__dict__.setdefault("_decode_graphs", {})
         static_before = common.STATIC_SHAPES
         common.STATIC_SHAPES = True                                # label bookkeeping of fixed width: nothing reads a length on the host
         try:
-            k1 = ("s1", tuple(features.shape), beam_size)
-            if fuse is not None:                                   # the fused recursion reads this model's tables and these weights
-                k1 = k1 + (id(fuse[0]), fuse[1], fuse[2], True)
-                if len(fuse) == 4:                                 # and the biased one this graph's: the object itself (it hashes by
-                    k1 = k1 + (fuse[3],)                           # identity), so the tables a capture points at live as long as it
-            out1 = _graph_call(cache, k1, lambda f, fl: self._rescore_stage1(f, fl, beam_size, fuse), (features, features_length))
-            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, *bias = out1
+            k1 = ("s1", tuple(features.shape), spec)
+            encoder_out, encoder_mask, pre, plen, ctc_scores, bad, bias = _graph_call(
+                cache, k1, lambda f, fl: self._rescore_stage1(f, fl, spec), (features, features_length))
             Lm = max(int(plen.max()), 1)
             hip.check_prefix_beam_status(bad)
             Lb = min(-(-Lm // 16) * 16, pre.shape[1])
-            k2 = ("s2", tuple(encoder_out.shape), beam_size, Lb, float(ctc_weight), float(reverse_weight), id(lm), float(lm_weight))
-            if bias:                                               # one more input: a graph of its own
-                k2 = k2 + ("bias",)
+            k2 = ("s2", tuple(encoder_out.shape), beam_size, Lb, float(ctc_weight), float(reverse_weight), lm, float(lm_weight),
+                  bias is not None)                                # (a bias is one more input: a graph of its own)
             toks, n, mean_len = _graph_call(
-                cache, k2, lambda eo, em, p, pl, cs, *bi: self._rescore_stage2(eo, em, p, pl, cs, Lb, beam_size, ctc_weight, reverse_weight,
-                                                                              lm, lm_weight, *bi),
-                (encoder_out, encoder_mask, pre, plen, ctc_scores, *bias))
+                cache, k2, lambda *a: self._rescore_stage2(*a[:5], Lb, beam_size, ctc_weight, reverse_weight, lm, lm_weight, a[5]),
+                (encoder_out, encoder_mask, pre, plen, ctc_scores, bias))
         finally:
             common.STATIC_SHAPES = static_before
         self.last_nbest_mean_len = float(mean_len)

@@ -16,16 +16,13 @@ class PrefixBeamStream:
 
     def __init__(self, B: int, beam: int, max_len: int, device, lm=None, context=None, lm_weight: float = 0.0,
                  length_bonus: float = 0.0, eos: bool = True, final: bool = True):
-        if not 1 <= beam <= 16:
-            raise ValueError(f"PrefixBeamStream: beam must be 1..16 (got {beam})")
+        self.spec = hip.PrefixSearch(beam, lm, context, lm_weight, length_bonus, eos, final)
+        self.spec.validate("PrefixBeamStream", True)
         if B < 1 or max_len < 1:
             raise ValueError(f"PrefixBeamStream: bad shape B={B} max_len={max_len}")
         self.B, self.beam, self.max_len, self.device = B, beam, max_len, torch.device(device)
-        self.lm, self.context = lm, context
-        self.weights = dict(lm_weight=lm_weight, length_bonus=length_bonus, eos=eos, final=final)
         dev = self.device
-        self._lm = None if lm is None else hip.ngram_model(lm, dev)
-        self._ctx = None if context is None else hip.context_graph(context, dev)
+        self._abi = self.spec.abi(dev)
         n = hip.lib().oe_ctc_prefix_beam_state_bytes(B, beam, max_len)
         self._states = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.stable_prefix = torch.zeros(B, max_len, dtype=torch.int32, device=dev)
@@ -35,8 +32,15 @@ class PrefixBeamStream:
         self.frames = torch.zeros(B, beam, max_len, dtype=torch.int32, device=dev)
         self.plen = torch.full((B, beam), -1, dtype=torch.int32, device=dev)
         self.total, self.ctc, self.lms, self.bias = (torch.zeros(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
+        # what the kernel is handed of the four, and what a result shows: an unwritten buffer stays zero, plain: ctc is the total
+        self._outs, self.scores = self.spec.bind(dict(zip(hip.SCORES, (self.total, self.ctc, self.lms, self.bias))))
         self._ws, self._ws_T = None, -1
         self.reset()
+
+    @classmethod
+    def of(cls, spec, B: int, max_len: int, device):
+        """The stream of `spec`, a hip.PrefixSearch built elsewhere."""
+        return cls(B, spec.beam, max_len, device, spec.lm, spec.context, spec.lm_weight, spec.length_bonus, spec.eos, spec.final)
 
     def reset(self):
         """Back to the empty prefix: the next push starts a new search."""
@@ -74,18 +78,14 @@ class PrefixBeamStream:
         if lens is not None:
             lens = lens.to(device=self.device, dtype=torch.int32).contiguous()
         ws, status = self._workspace(top_logp.shape[1])
-        plain = self._lm is None and self._ctx is None
-        a = hip.prefix_beam_args(top_logp, top_idx, lens, self.beam, self.max_len, ws, self.prefixes, self.plen, self.total,
-                                 None if plain else self.ctc, None if self._lm is None else self.lms,
-                                 None if self._ctx is None else self.bias, lm=self._lm, ctx=self._ctx,
-                                 **self.weights)
+        a = hip.prefix_beam_args(top_logp, top_idx, lens, self.beam, self.max_len, ws, self.prefixes, self.plen, *self._outs,
+                                 **self._abi)
         out = self._states[self._flip]
         hip.prefix_beam_chunk(a, self._cur, out, self.stable_prefix, self.stable_frame, self.stable_len, self.frames, last=last, emit=emit)
         self._cur, self._flip = out, self._flip ^ 1
         self.done = bool(last)
         wrote = emit or last
-        tensors = dict(prefixes=self.prefixes, frames=self.frames, plen=self.plen, total=self.total,
-                       ctc=self.total if plain else self.ctc, lm=self.lms, bias=self.bias, stable_prefix=self.stable_prefix,
+        tensors = dict(prefixes=self.prefixes, frames=self.frames, plen=self.plen, **self.scores, stable_prefix=self.stable_prefix,
                        stable_frame=self.stable_frame, stable_len=self.stable_len, status=status)
         if raw:
             return tensors
@@ -96,7 +96,7 @@ class PrefixBeamStream:
             plen = self.plen.cpu().numpy()
             width = max(int(plen.max()), 1)
             pre, frm = self.prefixes[:, :, :width].cpu().numpy(), self.frames[:, :, :width].cpu().numpy()
-            sc = [tensors[k].cpu().numpy() for k in ("total", "ctc", "lm", "bias")]
+            sc = [self.scores[k].cpu().numpy() for k in hip.SCORES]
         for b in range(self.B):
             nbest, frames = [], []
             if wrote:
@@ -104,9 +104,7 @@ class PrefixBeamStream:
                     n = int(plen[b, i])
                     if n < 0:
                         continue
-                    total, ctc, lm, bias = (float(s[b, i]) for s in sc)
-                    nbest.append((tuple(pre[b, i, :n].tolist()), total, ctc if not plain else total, lm if self._lm is not None else 0.0,
-                                  bias if self._ctx is not None else 0.0))
+                    nbest.append((tuple(pre[b, i, :n].tolist()), *(float(s[b, i]) for s in sc)))
                     frames.append(frm[b, i, :n].tolist())
             res.append({"nbest": nbest, "frames": frames, "stable": stable[b]})
         return res

@@ -5,6 +5,9 @@ the product and held to what is pinned by tests/test_ctc_bias_beam_ref.py), run 
 Bounds, those of tests/test_ctc_lm_beam_gpu.py: the same prefixes in the same order, exactly (the cases keep neighbouring
 totals 1e-8 apart or exactly equal, asserted again on the top-k really used); total and ctc within 1e-9 * max(1, |x|); lm
 within 2**-52 * n * S.  bias is EXACTLY equal: both sides add the same float32 values in float64 in the same order."""
+import gc
+import weakref
+
 import numpy as np
 import pytest
 import torch
@@ -15,6 +18,7 @@ import ctc_bias_beam_ref as BR  # noqa: E402
 import ctc_lm_beam_ref as R  # noqa: E402
 import ngram_ref  # noqa: E402
 from test_ctc_lm_beam_gpu import _built_lm, _close, _model, _ragged  # noqa: E402
+from openeat_amd.hip import PrefixSearch  # noqa: E402
 from openeat_amd.models.ngram_lm import NgramLM  # noqa: E402
 from openeat_amd.utils.context_graph import ContextGraph  # noqa: E402
 
@@ -302,7 +306,8 @@ def test_rescoring_with_a_context_graph(tmp_path, monkeypatch):
         keys_before = set(model._decode_graphs)
         none = model.attention_rescoring_batch(feats, flen, beam, use_graphs=False, context=None, **kw)
         none_g = model.attention_rescoring_batch(feats, flen, beam, use_graphs=True, context=None, **kw)
-        assert set(model._decode_graphs) == keys_before and all(len(k) == 3 for k in keys_before if k[0] == "s1")
+        assert set(model._decode_graphs) == keys_before                     # and the search in the key has neither LM nor graph
+        assert all(len(k) == 3 and k[2] == PrefixSearch(beam) for k in keys_before if k[0] == "s1")
         eager = model.attention_rescoring_batch(feats, flen, beam, use_graphs=False, context=graph, **kw)
         first = model.attention_rescoring_batch(feats, flen, beam, use_graphs=True, context=graph, **kw)
         replay = model.attention_rescoring_batch(feats, flen, beam, use_graphs=True, context=graph, **kw)
@@ -316,14 +321,18 @@ def test_rescoring_with_a_context_graph(tmp_path, monkeypatch):
     for b in range(len(eager)):
         assert tuple(eager[b]) in {h[0] for h in nbest[b]}, (b, eager[b])
         assert tuple(eager_lm[b]) in {h[0] for h in nbest_lm[b]}, (b, eager_lm[b])
-    keys = [k for k in model._decode_graphs if k[0] == "s1"]
-    assert any(len(k) == 8 and k[3:7] == (id(None), 0.0, 0.0, True) and k[7] is graph for k in keys)      # the key holds the graph itself:
-    assert any(len(k) == 8 and k[3:7] == (id(lm), 0.7, 0.4, True) and k[7] is graph for k in keys)        # its tables outlive no capture
+    specs = [k[2] for k in model._decode_graphs if k[0] == "s1"]
+    assert any(s.lm is None and (s.lm_weight, s.length_bonus, s.eos) == (0.0, 0.0, True) and s.context is graph for s in specs)
+    assert any(s.lm is lm and (s.lm_weight, s.length_bonus, s.eos) == (0.7, 0.4, True) and s.context is graph for s in specs)
     with pytest.raises(ValueError):
         model.attention_rescoring_batch(feats, flen, 17, context=graph, **kw)
     monkeypatch.setattr(asr_model, "DEVICE_BEAM", False)
     with pytest.raises(ValueError):
         model.attention_rescoring_batch(feats, flen, beam, context=graph, **kw)
+    alive = weakref.ref(lm)                                                 # the keys hold the LM and the graph themselves: the
+    del lm, kw, specs                                                       # tables a cached capture points at outlive the caller's
+    gc.collect()
+    assert any(k[0] == "s1" and k[2].lm is alive() is not None for k in model._decode_graphs)
 
 
 def test_stage_two_adds_the_final_bias(tmp_path):
@@ -343,7 +352,7 @@ def test_stage_two_adds_the_final_bias(tmp_path):
         nbest = model.ctc_context_beam_search(feats, flen, beam, graph)
         want = torch.tensor([[nb[i][4] if i < len(nb) else NEG for i in range(beam)] for nb in nbest], dtype=torch.float64)
         assert len(seen) == 1 and torch.equal(seen[0].cpu().view(B, beam), want) and float(want[want > NEG].abs().sum()) > 0.0
-        encoder_out, encoder_mask, pre, plen, ctc, bad, bias = model._rescore_stage1(feats, flen, beam, (None, 0.0, 0.0, graph))
+        encoder_out, encoder_mask, pre, plen, ctc, bad, bias = model._rescore_stage1(feats, flen, PrefixSearch(beam, None, graph))
         Lm = max(int(plen.max()), 1)
         assert int(bad[0]) == 0
         for slot in range(beam):
@@ -354,3 +363,43 @@ def test_stage_two_adds_the_final_bias(tmp_path):
             for b in range(B):
                 if slot < len(nbest[b]):
                     assert tuple(toks[b, : n[b]].tolist()) == nbest[b][slot][0], (slot, b)
+
+
+def test_stage_one_is_the_public_search_on_the_same_top_k(tmp_path):
+    """_rescore_stage1(spec) for the plain, the LM-fused, the biased and the LM-fused biased search: prefixes (within their
+    lengths), lengths, CTC scores and bias are what the matching public hip.ctc_prefix_beam_*_device(raw=True) returns on the
+    same top-k, bit for bit; no bias without a graph; the status word is 0."""
+    from openeat_amd import hip, ops
+    model, V = _model()
+    lm, _, _ = _built_lm(tmp_path, V, 51)
+    graph = _device_graph(_model_graph(V))
+    feats, flen = _ragged(41, [97, 83, 64, 41, 23])
+    B, beam, lw, lb = 5, 4, 0.7, 0.4
+    with torch.no_grad():
+        encoder_out, encoder_mask, _ = model._encode(feats, flen)
+        lens = encoder_mask.squeeze(1).sum(1).to(torch.int32)
+        top_p, top_i = ops.topk_rows(model.ctc.logits(encoder_out), beam, log_softmax=True)
+        plain = hip.ctc_prefix_beam_device(top_p, top_i, lens, beam, raw=True)
+        fused = hip.ctc_prefix_beam_lm_device(top_p, top_i, lens, beam, lm, lw, lb, raw=True)
+        biased = hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens, beam, graph, None, 0.0, lb, raw=True)
+        both = hip.ctc_prefix_beam_ctx_device(top_p, top_i, lens, beam, graph, lm, lw, lb, raw=True)
+        # (spec; the public search's prefixes, lengths, CTC scores, bias, status word)
+        cases = [(PrefixSearch(beam), plain[0], plain[1], plain[2], None, plain[3]),
+                 (PrefixSearch(beam, lm, None, lw, lb), fused[0], fused[1], fused[3], None, fused[5]),
+                 (PrefixSearch(beam, None, graph, 0.0, lb), biased[0], biased[1], biased[3], biased[5], biased[6]),
+                 (PrefixSearch(beam, lm, graph, lw, lb), both[0], both[1], both[3], both[5], both[6])]
+        fired = 0
+        for spec, w_pre, w_plen, w_ctc, w_bias, w_bad in cases:
+            where = spec.plan
+            enc, mask, pre, plen, ctc, bad, bias = model._rescore_stage1(feats, flen, spec)
+            assert int(bad[0]) == 0 and int(w_bad[0]) == 0, where
+            assert pre.shape == (B * beam, w_pre.shape[2]) and plen.shape == ctc.shape == (B * beam,), where
+            assert torch.equal(plen.view(B, beam), w_plen) and int((w_plen >= 0).sum()) > 0, where
+            assert torch.equal(_used(pre.view(B, beam, -1), w_plen), _used(w_pre, w_plen)), where
+            assert torch.equal(ctc.view(B, beam), w_ctc) and torch.equal(_bits(ctc.view(B, beam)), _bits(w_ctc)), where
+            if w_bias is None:
+                assert bias is None, where
+            else:
+                assert bias.shape == (B * beam,) and torch.equal(_bits(bias.view(B, beam)), _bits(w_bias)), where
+                fired += int((w_bias[w_plen >= 0] != 0).sum())
+        assert fired > 0                                                    # the graph's phrases really scored

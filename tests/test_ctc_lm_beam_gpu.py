@@ -6,6 +6,9 @@ Bounds: the same prefixes in the same order, exactly (the cases keep neighbourin
 the yardstick reports and this file asserts again on the top-k it really used); total and ctc within 1e-9 * max(1, |x|)
 (device exp / log, as the plain device-beam test allows); lm within 2**-52 * n * S, n float32 values of summed magnitude S
 (both sides add the same float32 values in float64), the bound of tests/test_ngram_gpu.py."""
+import gc
+import weakref
+
 import numpy as np
 import pytest
 import torch
@@ -259,10 +262,15 @@ def test_rescoring_with_first_pass_lm(tmp_path, monkeypatch):
     for b, h in enumerate(default_w):                                     # the first-pass weight defaults to lm_weight
         assert tuple(h) in {p for p, _, _, _ in nbest_w[b]}, (b, h)
     assert off == parent and off_g == parent
-    keys = [k for k in model._decode_graphs if k[0] == "s1"]
-    assert any(len(k) == 3 for k in keys) and any(len(k) == 7 and k[3] == id(lm) and k[4:] == (0.7, 0.4, True) for k in keys)
+    specs = [k[2] for k in model._decode_graphs if k[0] == "s1"]
+    assert any(s.plain for s in specs)
+    assert any(s.lm is lm and s.context is None and (s.lm_weight, s.length_bonus, s.eos) == (0.7, 0.4, True) for s in specs)
     with pytest.raises(ValueError):
         model.attention_rescoring_batch(feats, flen, 17, **kw, **fp)
     monkeypatch.setattr(asr_model, "DEVICE_BEAM", False)
     with pytest.raises(ValueError):
         model.attention_rescoring_batch(feats, flen, beam, **kw, **fp)
+    alive = weakref.ref(lm)                                                 # the key holds the LM itself: the tables a cached capture
+    del lm, kw, specs                                                       # points at outlive the caller's reference
+    gc.collect()
+    assert any(k[0] == "s1" and k[2].lm is alive() is not None for k in model._decode_graphs)

@@ -378,7 +378,7 @@ def test_model_error_counts_attention_rescoring_and_oracle():
         plain = model.error_counts(feats, flen, tg, tl, mode="attention_rescoring", beam_size=beam)
         assert set(plain) == {"counts"} and torch.equal(plain["counts"], out["counts"])
         with torch.no_grad():
-            _, _, pre, plen, _, _ = model._rescore_stage1(feats, flen, beam)
+            _, _, pre, plen, _, _, _ = model._rescore_stage1(feats, flen, hip.PrefixSearch(beam))
         pre, plen = pre.cpu(), plen.cpu().tolist()
         oracle, index = out["oracle_counts"].cpu().tolist(), out["oracle_index"].cpu().tolist()
         for b, t in enumerate(tgt):

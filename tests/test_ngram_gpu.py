@@ -4,6 +4,9 @@ against the one-utterance API, which scores on the host with NgramLM.score (held
 
 Bounds: matched orders exactly; values within 2**-52 * n * S, n = how many float32 values the yardstick summed for the
 sentence and S the sum of their magnitudes - both sides add the same float32 values in float64, only the order differs."""
+import gc
+import weakref
+
 import numpy as np
 import pytest
 import torch
@@ -244,4 +247,8 @@ def test_ngram_rescoring_from_graphs_and_host_beam_equal_eager(tmp_path, gemm_pr
     assert host_a == want_a
     assert want_a != want_b and want_a != plain                        # the two models really pick differently
     recs = model._decode_graphs
-    assert sum(1 for k, v in recs.items() if k[0] == "s2" and v is not None and k[6] in (id(lm_a), id(lm_b))) >= 2
+    assert sum(1 for k, v in recs.items() if k[0] == "s2" and v is not None and (k[6] is lm_a or k[6] is lm_b)) >= 2
+    alive = weakref.ref(lm_a)                                          # the key holds the LM itself: the tables a cached capture
+    del lm_a, recs                                                     # points at outlive the caller's reference
+    gc.collect()
+    assert any(k[0] == "s2" and k[6] is alive() is not None for k in model._decode_graphs)

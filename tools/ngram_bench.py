@@ -102,7 +102,7 @@ def stage2_part():
     feats = torch.randn(B, 998, 80, device=DEV)
     flen = torch.full((B,), 998, dtype=torch.int32, device=DEV)
     with torch.no_grad():
-        enc, mask, pre, plen, ctc, bad = model._rescore_stage1(feats, flen, beam)
+        enc, mask, pre, plen, ctc, bad, _ = model._rescore_stage1(feats, flen, hip.PrefixSearch(beam))
         Lm = max(int(plen.max()), 1)
         Lb = min(-(-Lm // 16) * 16, pre.shape[1])
         print(f"stage 2 at B={B} x 998 frames, beam {beam}: T'={enc.shape[1]}, R={B * beam}, longest hypothesis {Lm} (width {Lb}), "
