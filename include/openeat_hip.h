@@ -786,6 +786,34 @@ typedef struct oe_context_graph {
     float c;
 } oe_context_graph;
 
+/* The hotword bias of C candidate next tokens of each of R growing hypotheses: what a search step that extends hypotheses
+ * token by token adds to its pruning key - the counterpart of oe_ngram_next for an oe_context_graph.  hits(p), k(p) and
+ * bias(p) are those of the biased prefix search, stated under oe_ctc_prefix_beam below; step(s, token) is the automaton's
+ * transition as oe_context_graph describes it (the edge, on a miss fail and again).
+ * Rows: row r is a hypothesis g that sits in automaton state state[r] ((R) i32; the root, 0, for the empty one) with
+ * hits[r] = hits(g) ((R) f64).  A state[r] outside 0..n_states-1, negative ones included = the slot does not exist: its whole
+ * row is out_state = -1, out_hits = out_bias = -inf.
+ * Candidates: cand (R, C) i32, entry [r, j] is for token cand[r, j];  cand == NULL = every token: entry [r, j] is for token j
+ * and C is the vocabulary size.  A token no edge carries - the blank, a negative id, an id beyond the vocabulary - is an
+ * ordinary mismatch: the walk follows fail to wherever it ends; the key is built from the unsigned token.
+ * A candidate other than eos_tok:  s' = step(state[r], token);  h' = hits[r] + the scores of the phrases that end at s',
+ *   added one by one in float64 in the list order s', link[s'], .. (longest first);
+ *   out_state = s', out_hits = h' = hits(g . token), out_bias = h' + (double)c * pend[s'] = bias(g . token) during the search.
+ * The eos_tok candidate (-1: no token is): it is not walked - the hypothesis ends, so the pending credit is dropped as
+ *   `final` drops it:  out_state = state[r], out_hits = hits[r], out_bias = hits[r].
+ * out_state (R, C) i32 and out_hits (R, C) f64 may both be NULL and are then not written (a pre-selection over the whole
+ * vocabulary needs out_bias only); one without the other is refused.  out_bias (R, C) f64.
+ * An entry is the same bits whether its token is reached through cand or through the full-vocabulary form, and for any grid
+ * shape; out_hits and out_bias are bit for bit ContextGraph.bias of the extended prefix on the host (final = True and
+ * final = False), for the eos_tok candidate out_bias is that of the un-extended prefix with final = True.
+ * Refused before any launch (oe_last_error): a null pointer other than cand, out_state or out_hits (the graph's among them),
+ * R < 0, C < 1, eos_tok < -1, and what oe_ctc_prefix_beam refuses about an oe_context_graph: n_states outside 1..2^20, a
+ * capacity that is no power of two >= 2, a bad max_probe, a non-finite or negative c.  R == 0 returns 0 without a launch.
+ * Every index read from a table is checked against n_states.
+ * One launch, no workspace, no atomics, no allocation, no host read: capturable. */
+int oe_context_next(const oe_context_graph* ctx, const int* state, const double* hits, int R, const int* cand, int C,
+                    int eos_tok, int* out_state, double* out_hits, double* out_bias, void* stream);
+
 /* CTC prefix beam search on the device, one wavefront per utterance (asr_model.py:359-396; the host functions below are
  * the same algorithm on the CPU and serve as its checker): plain, with n-gram LM shallow fusion (lm != NULL), with hotword
  * biasing (ctx != NULL), or with both.  One entry point, one argument struct, four instantiations of one kernel:

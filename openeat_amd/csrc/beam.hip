@@ -66,6 +66,7 @@
 #include "oe_common.h"
 #include "../../include/openeat_hip.h"
 #include "ngram_common.h"
+#include "context_common.h"
 
 #define PB_MAXBEAM 16
 #define PB_MAXC ((PB_MAXBEAM * PB_MAXBEAM + 63) / 64)          // (token, hypothesis) pairs per lane
@@ -107,12 +108,6 @@ __device__ __forceinline__ double pb_total_ctx(double ctc, double lm, int len, d
     if constexpr (LM) return pb_total(ctc, lm, len, lm_weight, length_bonus) + bias;
     const double c = length_bonus * (double)len;
     return (ctc + c) + bias;
-}
-// hits + (double)c * k, the product rounded before the sum
-__device__ __forceinline__ double pb_bias(double hits, float c, int k) {
-#pragma clang fp contract(off)
-    const double credit = (double)c * (double)k;
-    return hits + credit;
 }
 
 // log10 p(w | the prefix whose state is ent / bo); ent_out / bo_out (or null): the state of prefix + w
@@ -166,40 +161,14 @@ struct PbLmArgs {       // what the fusion takes on top of the plain search (all
     double* __restrict__ out_lm;
 };
 
-struct PbCtxArgs : PbLmArgs {       // what the biased search takes on top of that: the context graph (openeat_hip.h)
-    const uint4* __restrict__ edges;
-    unsigned long long edge_mask;   // capacity - 1
-    const int* __restrict__ fail;
-    const int2* __restrict__ out;   // (score bits, link)
-    const int* __restrict__ pend;
-    int edge_max_probe, n_states, final;
-    float c;
+// what the biased search takes on top of that: the context graph (openeat_hip.h; CtxGraph and the automaton's step
+// pb_ctx_step: context_common.h)
+struct PbCtxArgs : PbLmArgs, CtxGraph {
+    int final;
     double* __restrict__ out_bias;
 };
 template <bool CTX> struct PbArgsOf { typedef PbLmArgs type; };          // the two searches without a graph keep their arguments
 template <> struct PbArgsOf<true> { typedef PbCtxArgs type; };
-
-// The automaton's step for a prefix that sits in `state` and takes token `tok`: the new state; hits grows by the scores of
-// the phrases that end there, longest first.  Every index read from a table is checked against n_states.
-__device__ __forceinline__ int pb_ctx_step(const PbCtxArgs& g, int state, int tok, double& hits) {
-    int ns = 0;
-    for (int d = 0; d <= 32; ++d) {                                // depth falls with every fail link: <= 32 of them, 33 probes
-        float nxt, unused;
-        const unsigned long long key = ((unsigned long long)(unsigned)state << 32) | (unsigned)tok;
-        if (ng_find(g.edges, g.edge_mask, g.edge_max_probe, key, nxt, unused) >= 0) { ns = __float_as_int(nxt); break; }
-        if (state == 0) break;
-        state = g.fail[state];
-        if ((unsigned)state >= (unsigned)g.n_states) break;
-    }
-    if ((unsigned)ns >= (unsigned)g.n_states) ns = 0;
-    int t = ns;
-    for (int d = 0; d < 32 && t > 0 && t < g.n_states; ++d) {
-        const int2 o = g.out[t];
-        hits = hits + (double)__int_as_float(o.x);
-        t = o.y;
-    }
-    return ns;
-}
 
 // ---- the resumable search (CHUNK = true; oe_ctc_prefix_beam_chunk, semantics in include/openeat_hip.h) -------------------
 // The state of a search between two chunks, device memory: a header of 8 ints (magic, B, beam, max_len, variant = LM | CTX << 1)
@@ -753,13 +722,7 @@ static int pb_prepare(const char* fn, const oe_prefix_beam_args& a, PbCtxArgs& l
                    "%s: the plain search has no lm_weight or length_bonus term (got %g and %g): both must be 0", fn, a.lm_weight, a.length_bonus);
     }
     if (g) {
-        OE_REQUIRE(g->n_states >= 1 && g->n_states <= (1 << 20), "%s: n_states must be 1..2^20 (got %d)", fn, g->n_states);
-        OE_REQUIRE(g->capacity >= 2 && (g->capacity & (g->capacity - 1)) == 0, "%s: the graph's capacity must be a power of two >= 2 (got %ld)",
-                   fn, g->capacity);
-        OE_REQUIRE(g->max_probe >= 0 && g->max_probe < g->capacity, "%s: bad max_probe %d of the graph", fn, g->max_probe);
-        OE_REQUIRE(isfinite(g->c) && g->c >= 0.f, "%s: the partial credit c must be finite and >= 0", fn);
-        la.edges = (const uint4*)g->edges; la.edge_mask = (unsigned long long)(g->capacity - 1); la.edge_max_probe = g->max_probe;
-        la.fail = g->fail; la.out = (const int2*)g->out; la.pend = g->pend; la.n_states = g->n_states; la.c = g->c;
+        if (ctx_graph_args(fn, g, &la)) return -1;
         la.final = a.final; la.out_bias = a.out_bias;
     }
     return 0;

@@ -313,6 +313,7 @@ _SIGNATURES = {
     "oe_ctc_prefix_beam_host_batch": (I, [P, P, I, I, P, I, I, P, P, P, I]),
     "oe_ngram_score": (I, [C.POINTER(NgramModel), P, L, P, I, I, I, P, P, P, P]),
     "oe_ngram_next": (I, [C.POINTER(NgramModel), P, L, P, I, P, I, I, P, P]),
+    "oe_context_next": (I, [C.POINTER(ContextGraph), P, P, I, P, I, I, P, P, P, P]),
     "oe_edit_distance_workspace_bytes": (SZ, [I, I, I]),
     "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_ctc_prefix_score_init": (I, [P, P, I, I, I, L, I, I, P, P]),

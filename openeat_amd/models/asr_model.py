@@ -812,7 +812,7 @@ class ASRModel(torch.nn.Module):
     def ctc_attention_beam_search(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int = 10,
                                   ctc_weight: float = 0.3, length_bonus: float = 0.0, ctc_candidates: Optional[int] = None,
                                   max_len: Optional[int] = None, nbest: bool = False, lm=None, lm_weight: float = 0.0,
-                                  lm_prebeam: bool = True):
+                                  lm_prebeam: bool = True, context=None, context_prebeam: bool = True):
         """Joint CTC/attention one-pass beam search (not in the reference; semantics in utils/joint_search.py and, for the CTC
         prefix score, include/openeat_hip.h): the decoder proposes `ctc_candidates` tokens per hypothesis (default
         min(2 beam_size, V, 64)), and each is ranked by (1 - ctc_weight) * attention + ctc_weight * CTC prefix score +
@@ -825,7 +825,14 @@ class ASRModel(torch.nn.Module):
         lm (an NgramLM over this model's vocab_size tokens), lm_weight, lm_prebeam: n-gram LM fusion inside the search - the
         total gains lm_weight * the hypothesis' LM score (log10, </s> included once it is finished), one oe_ngram_next launch
         per step; lm_prebeam: the LM also takes part in choosing the candidates (utils/joint_search.py).  With an LM the
-        nbest entries are (tokens, total, att, ctc, lm)."""
+        nbest entries are (tokens, total, att, ctc, lm).
+        context (a ContextGraph of hotword phrases over this model's tokens), context_prebeam: hotword biasing inside the
+        search - the total gains the hypothesis' bias (hits + the pending partial credit, which <eos> drops;
+        include/openeat_hip.h), one oe_context_next launch per step; context_prebeam: the bias also takes part in choosing the
+        candidates, at the price of one more launch over the whole vocabulary (utils/joint_search.py).  A phrase with a
+        token id >= vocab_size or with <eos> could never fire and is refused.  With a graph the nbest entries gain a last
+        element, bias: (tokens, total, att, ctc[, lm], bias)."""
+        from openeat_amd.utils.context_graph import ContextGraph
         from openeat_amd.utils.joint_search import joint_beam_search
         if not 0.0 <= ctc_weight <= 1.0:
             raise ValueError(f"ctc_weight must lie in [0, 1] (got {ctc_weight})")
@@ -843,6 +850,13 @@ class ASRModel(torch.nn.Module):
                 raise ValueError(f"lm_weight must be finite (got {lm_weight})")
             if len(lm.tok2word) != self.vocab_size:
                 raise ValueError(f"the LM maps {len(lm.tok2word)} tokens, the model has {self.vocab_size}")
+        if context is not None:
+            if not isinstance(context, ContextGraph):
+                raise ValueError(f"context must be a ContextGraph (got {type(context).__name__})")
+            for q in context.phrases:
+                if any(t >= self.vocab_size or t == self.eos for t in q):
+                    raise ValueError(f"hotword phrase {list(q)} holds <eos> ({self.eos}) or a token id >= vocab_size ({self.vocab_size}): "
+                                     "it can never fire")
         assert features.shape[0] == features_length.shape[0]
         device = features.device
         encoder_out, encoder_mask, _ = self._encode(features, features_length)
@@ -863,11 +877,12 @@ class ASRModel(torch.nn.Module):
             p, cache, _ = self.decoder.forward_one_step(hyps, hyps_mask, memory, memory_mask, cache=cache)
             return ops.log_softmax_rows(p)
 
+        kw = {} if context is None else dict(context=context, context_prebeam=context_prebeam)
         if lm is None:
-            res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len)
+            res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len, **kw)
         else:
             res = joint_beam_search(logp, lens, step_fn, beam_size, C, self.eos, ctc_weight, length_bonus, max_len, 0, lm,
-                                    float(lm_weight), lm_prebeam)
+                                    float(lm_weight), lm_prebeam, **kw)
         if nbest:
             return [[h[:4] + h[5:] for h in nb] for nb in res]
         return [nb[0][0] if nb else [] for nb in res]

@@ -2450,6 +2450,43 @@ def ngram_next(lm, tokens, lens, cand=None, eos=None):
     return out
 
 
+def context_next(graph, state, hits, cand=None, eos=None, V=None, want_state: bool = True):
+    """The hotword bias of candidate next tokens of R growing hypotheses (oe_context_next; semantics in
+    include/openeat_hip.h): `graph` an openeat_amd.utils.context_graph.ContextGraph, state (R) integer automaton states (0: the
+    root; outside the graph's states: the slot does not exist, its row is -1 / -inf) and hits (R) float64 on the device,
+    cand (R, C) integer token ids or None = every token of a vocabulary of V (required then), eos the token id that ends a
+    hypothesis (None: no token does) -> (state' (R, C) int32, hits' (R, C) float64, bias' (R, C) float64), the bits of
+    ContextGraph.bias of the extended prefix; want_state=False: bias' alone.
+    No host read, no allocation beyond the outputs: capturable."""
+    from openeat_amd.utils.context_graph import ContextGraph
+    if not isinstance(graph, ContextGraph):
+        raise TypeError(f"context_next: graph must be an openeat_amd.utils.context_graph.ContextGraph (got {type(graph).__name__})")
+    ts = (state, hits) if cand is None else (state, hits, cand)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError("context_next: openeat_amd ops need CUDA tensors; there is no CPU fallback (on the host: ContextGraph.bias)")
+    ints = (state,) if cand is None else (state, cand)
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ints) or hits.dtype != torch.float64 or state.dim() != 1 \
+            or hits.shape != state.shape or (cand is not None and (cand.dim() != 2 or cand.shape[0] != state.shape[0])):
+        raise TypeError("context_next: state (R) and cand (R, C) must be integer tensors, hits (R) a float64 tensor")
+    if cand is None and V is None:
+        raise ValueError("context_next: without cand every token is a candidate: V, the vocabulary size, is required")
+    dev = state.device
+    R = int(state.shape[0])
+    C = int(V) if cand is None else int(cand.shape[1])
+    if C < 1:
+        raise ValueError("context_next: at least one candidate per hypothesis (cand (R, C) with C >= 1, or V >= 1)")
+    eos = -1 if eos is None else int(eos)
+    if eos < -1:
+        raise ValueError(f"context_next: eos {eos} is no token id (None: no token ends a hypothesis)")
+    bias = torch.empty(R, C, dtype=torch.float64, device=dev)
+    new_state = torch.empty(R, C, dtype=torch.int32, device=dev) if want_state else None
+    new_hits = torch.empty(R, C, dtype=torch.float64, device=dev) if want_state else None
+    if R:
+        hip.call("oe_context_next", hip.context_graph(graph, dev), state.to(torch.int32).contiguous(), hits.contiguous(), R,
+                 None if cand is None else cand.to(torch.int32).contiguous(), C, eos, new_state, new_hits, bias)
+    return (new_state, new_hits, bias) if want_state else bias
+
+
 def edit_distance(ref, ref_lens, hyp, hyp_lens, group: int = 1, align: bool = False):
     """Edit distance of P (reference, hypothesis) pairs on the device (oe_edit_distance; semantics and tie order in
     include/openeat_hip.h): ref (P / group, Nmax) and hyp (P, Mmax) integer token ids, ref_lens (P / group) and hyp_lens (P)

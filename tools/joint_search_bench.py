@@ -4,6 +4,7 @@ search, and recognize at the same beam on the same batch.
 
   python tools/joint_search_bench.py                # 64 utterances x 10 s (249 encoder frames), beam 10, 20 candidates, V 3246
   python tools/joint_search_bench.py --lm-order 3   # also (iii) and the search with an n-gram LM of that order (0 = off)
+  python tools/joint_search_bench.py --hotwords 1000  # also (iv) and the search with a context graph of that many phrases
 
 (i)  oe_ctc_prefix_score alone, 640 hypotheses x 20 candidates x 249 frames, on hypotheses three tokens deep (their states come
      from the kernel itself), with and without the candidates' states.  The CTC log-probabilities are the log-softmax of random
@@ -17,7 +18,12 @@ search, and recognize at the same beam on the same batch.
      the candidate form (640 x 20, the top-20 of random attention scores) - timed as (i), and in (ii) the search at ctc_weight 0.3
      with the LM at lm_weight 0.5, pre-selected with the LM (one full-vocabulary call per step) and without (one candidate call).
      The LM is synthetic and sized like an AISHELL character LM (tools/lm_beam_bench.py's: ~1 M n-grams over the 3246 tokens, a
-     32 MiB table), its values arbitrary: the searches with it take other paths through the vocabulary, not fewer steps."""
+     32 MiB table), its values arbitrary: the searches with it take other paths through the vocabulary, not fewer steps.
+(iv) --hotwords N: oe_context_next alone on 640 hypotheses, half of them in the root and half in random states of the automaton
+     - the candidate form (640 x 20, all three outputs) and the full-vocabulary form (640 x 3246, out_bias only) - timed as (i),
+     and in (ii) the search at ctc_weight 0.3 with the graph, pre-selected with the bias (one full-vocabulary and one candidate
+     call per step) and without (one candidate call); with --lm-order as well, the search with the LM and the graph together,
+     both pre-selected.  The graph is synthetic: N distinct random phrases of 2..6 tokens over the 3246 tokens, context_score 3."""
 import argparse
 import os
 import sys
@@ -97,7 +103,35 @@ def lm_leg(lm):
         print(f"  {name}: {mid:8.1f} us per call = {mid * 1e3 / n:6.2f} ns per term (runs {', '.join('%.1f' % x for x in r)})")
 
 
-def search_leg(lm=None):
+def synthetic_graph(n):
+    from openeat_amd.utils.context_graph import ContextGraph
+    g = torch.Generator().manual_seed(17)
+    phrases = set()
+    while len(phrases) < n:
+        phrases.add(tuple(torch.randint(1, V - 1, (int(torch.randint(2, 7, (1,), generator=g)),), generator=g).tolist()))
+    return ContextGraph(sorted(phrases), 3.0)
+
+
+def context_leg(graph):
+    g = torch.Generator().manual_seed(19)
+    R = B * BEAM
+    state = torch.randint(0, graph.n_states, (R,), generator=g, dtype=torch.int32)
+    state[::2] = 0
+    state = state.to(DEV)
+    hits = (torch.rand(R, generator=g, dtype=torch.float64) * 9.0).to(DEV)
+    _, cand = ops.topk_rows(ops.log_softmax_rows((torch.randn(R, V, generator=g) * 3.0).to(DEV)), C)
+    print(f"(iv) oe_context_next: {len(graph.phrases)} phrases, {graph.n_states} states, edge table {graph.capacity * 16 / 2 ** 10:.0f} KiB, "
+          f"max_probe {graph.max_probe}; {R} hypotheses, every second one in the root")
+    runs = {f"{C} candidates": [], f"every token ({V})": []}
+    for _ in range(3):
+        runs[f"{C} candidates"].append(timed(lambda: ops.context_next(graph, state, hits, cand, V - 1)))
+        runs[f"every token ({V})"].append(timed(lambda: ops.context_next(graph, state, hits, None, V - 1, V=V, want_state=False)))
+    for (name, r), n in zip(runs.items(), (R * C, R * V)):
+        mid = sorted(r)[1]
+        print(f"  {name}: {mid:8.1f} us per call = {mid * 1e3 / n:6.2f} ns per entry (runs {', '.join('%.1f' % x for x in r)})")
+
+
+def search_leg(lm=None, graph=None):
     torch.manual_seed(7)
     model = ASRModel(80, V, **MODEL_CONF).to(DEV).eval()
     g = torch.Generator().manual_seed(123)
@@ -119,6 +153,13 @@ def search_leg(lm=None):
         for name, pre in (("joint search, 0.3 + LM, prebeam", True), ("joint search, 0.3 + LM, top-C  ", False)):
             legs[name] = lambda pre=pre: model.ctc_attention_beam_search(feats, flen, BEAM, 0.3, ctc_candidates=C, lm=lm, lm_weight=0.5,
                                                                          lm_prebeam=pre)
+    if graph is not None:
+        for name, pre in (("joint search, 0.3 + hotwords, prebeam", True), ("joint search, 0.3 + hotwords, top-C  ", False)):
+            legs[name] = lambda pre=pre: model.ctc_attention_beam_search(feats, flen, BEAM, 0.3, ctc_candidates=C, context=graph,
+                                                                         context_prebeam=pre)
+        if lm is not None:
+            legs["joint search, 0.3 + LM + hotwords, prebeam"] = lambda: model.ctc_attention_beam_search(
+                feats, flen, BEAM, 0.3, ctc_candidates=C, lm=lm, lm_weight=0.5, lm_prebeam=True, context=graph, context_prebeam=True)
     runs = {k: [] for k in legs}
     with torch.no_grad():
         for it in range(4):
@@ -136,7 +177,7 @@ def search_leg(lm=None):
               f"(runs {', '.join('%.1f' % (x * 1e3) for x in r)})")
     a, b, c = list(mids.values())[:3]
     for name in list(mids)[3:]:
-        print(f"  {name.strip()} / joint (0.3): {mids[name] / a:.3f};  the LM side of a step: {(mids[name] - a) * 1e6 / steps:.1f} us")
+        print(f"  {name.strip()} / joint (0.3): {mids[name] / a:.3f};  what it adds to a step: {(mids[name] - a) * 1e6 / steps:.1f} us")
     print(f"  joint (0.3) / recognize: {a / c:.2f};  joint (0) / recognize: {b / c:.2f};  the CTC side of a step: {(a - b) * 1e6 / steps:.1f} us")
 
 
@@ -144,7 +185,10 @@ if __name__ == "__main__":
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--lm-order", type=int, default=0, help="also time oe_ngram_next and the search with a synthetic n-gram LM of this order (2..5; 0: off)")
+    ap.add_argument("--hotwords", type=int, default=0, help="also time oe_context_next and the search with a synthetic context graph of this many phrases (0: off)")
     args = ap.parse_args()
+    if args.hotwords < 0:
+        ap.error("--hotwords takes 0 or a number of phrases")
     if args.lm_order and not 2 <= args.lm_order <= 5:
         ap.error("--lm-order takes 0 or 2..5")
     lm = None
@@ -154,4 +198,7 @@ if __name__ == "__main__":
     kernel_leg(SECONDS * 25 - 1)
     if lm is not None:
         lm_leg(lm)
-    search_leg(lm)
+    graph = synthetic_graph(args.hotwords) if args.hotwords else None
+    if graph is not None:
+        context_leg(graph)
+    search_leg(lm, graph)
