@@ -1040,6 +1040,45 @@ int oe_ctc_prefix_score(const float* logp, const int* lens, int B, int Tmax, int
                         const int* hyp_len, const int* last_tok, const int* cand, int C, int blank, int eos, double* psi,
                         double* cand_state, void* stream);
 
+/* Differentiable n-best CTC scoring: the exact CTC log-likelihood of each of `group` hypotheses of an utterance and the
+ * gradient of a weighted sum of them with respect to the utterance's logits - the device half of minimum word error rate
+ * training over n-best lists (Prabhavalkar et al. 2018; utils/mwer.py, ASRModel.forward_mwer).  These are the semantics every
+ * layer refers to (ops.ctc_nbest_logp; the yardstick is tests/ctc_nbest_ref.py).
+ *
+ * There are R = B * group rows; row r belongs to utterance r / group; blank = 0.  logits (B, T, ldv >= V) f32 and hlens (B)
+ * i32 as oe_ctc_loss_fused (hlens is clamped to 0..T by the kernel).  hyps (R, hyp_ld >= Lmax) i32, hyp_lens (R) i32; a
+ * negative length = the slot does not exist (as out_len of oe_ctc_prefix_beam).  1 <= group <= 64, 0 <= Lmax <= 255.
+ *
+ * oe_ctc_nbest_score: logp (R) f32.  logp[r] is the natural log of the sum, over all alignments of the utterance's
+ *   Tb = hlens[b] frames that collapse to hypothesis r, of the product of the frames' softmax probabilities - the trellis of the
+ *   loss: blank, y1, blank, .., blank.  A row is INFEASIBLE if the slot does not exist, hyp_lens[r] > Lmax (a hypothesis is
+ *   never truncated), Tb == 0, Tb < length + the number of adjacent equal tokens, or a token within the length lies outside
+ *   1..V-1 (such a token is never used as an index).  An infeasible row has logp = -inf exactly and contributes nothing to
+ *   dlogits.  An empty hypothesis with Tb > 0 is feasible: every frame blank.  logp[r] depends on its own row only: permuting
+ *   the slots of a group permutes the bits of logp.  What lies at or behind a row's length never reaches a result.
+ *   saved: NULL, or oe_ctc_nbest_saved_bytes(B,T,group,Lmax) bytes, 16-byte aligned, opaque: what the forward keeps so that
+ *   oe_ctc_nbest_grad need not run the recursions again.  logp is bit-identical with and without it.
+ *   workspace: oe_ctc_nbest_workspace_bytes(B,T,group,Lmax) bytes, 16-byte aligned.
+ * oe_ctc_nbest_grad: the same logits, hlens, hyps, hyp_lens, group, Lmax as the score call that filled `saved`, and its logp;
+ *   g (R) f32 the weights.  For t < Tb and v < V
+ *     dlogits[b,t,v] = sum over the feasible rows r of b of  g[r] * (occ_r[t,v] - softmax(logits[b,t,:])[v]),
+ *   occ_r[t,v] the posterior probability that hypothesis r's alignment emits class v at frame t: the gradient of
+ *   sum_r g[r] * logp[r] with respect to the raw logits.  Rows t >= Tb are written as exact zeros; columns >= V are not
+ *   written.  g of an infeasible row is not read into any result (it may be NaN).  dlogits (B, T, ldv) may not alias logits.
+ *   workspace: not used by this call; NULL is allowed.
+ * Both calls: no float atomics, every sum in a fixed order (bit-identical from run to run); no allocation, no
+ * synchronisation, no host-side state: capturable.  Null required pointers, group or Lmax outside their ranges, ldv < V,
+ * hyp_ld < Lmax and dlogits == logits are reported through oe_last_error before any launch.
+ * Passes: score = one wave per frame reads the logits once (row statistics, log-probabilities at the hypotheses' states), then
+ * one block per row runs alpha and - with `saved` - beta and the occupancies; grad = one workgroup per dlogits row. */
+size_t oe_ctc_nbest_workspace_bytes(int B, int T, int group, int Lmax);
+size_t oe_ctc_nbest_saved_bytes(int B, int T, int group, int Lmax);
+int oe_ctc_nbest_score(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* hyps, long hyp_ld,
+                       const int* hyp_lens, int group, int Lmax, float* logp, void* saved, void* workspace, void* stream);
+int oe_ctc_nbest_grad(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* hyps, long hyp_ld,
+                      const int* hyp_lens, int group, int Lmax, const float* logp, const float* g, const void* saved,
+                      float* dlogits, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -318,6 +318,10 @@ _SIGNATURES = {
     "oe_edit_distance": (I, [P, L, P, I, P, L, P, I, I, I, P, P, P, P]),
     "oe_ctc_prefix_score_init": (I, [P, P, I, I, I, L, I, I, P, P]),
     "oe_ctc_prefix_score": (I, [P, P, I, I, I, L, I, P, P, P, P, I, I, I, P, P, P]),
+    "oe_ctc_nbest_workspace_bytes": (SZ, [I, I, I, I]),
+    "oe_ctc_nbest_saved_bytes": (SZ, [I, I, I, I]),
+    "oe_ctc_nbest_score": (I, [P, L, I, I, I, P, P, L, P, I, I, P, P, P, P]),
+    "oe_ctc_nbest_grad": (I, [P, L, I, I, I, P, P, L, P, I, I, P, P, P, P, P, P]),
     "oe_grad_norm_workspace_floats": (SZ, []),
     "oe_grad_norm": (I, [P, L, P, P, P]),
     "oe_adam_step": (I, [P, P, P, P, L, P, F, F, F, F, F, P, P, P]),

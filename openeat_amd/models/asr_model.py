@@ -160,6 +160,69 @@ class ASRModel(torch.nn.Module):
             return self._joint_loss(loss_ctc, l_loss, r_loss), acc
         return loss_ctc, None
 
+    def forward_mwer(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor, targets_length: torch.Tensor,
+                     nbest: int = 4, ce_weight: float = 0.01, nbest_lists=None):
+        """Minimum word error rate training step over the model's own n-best lists (Prabhavalkar et al. 2018; the reference
+        trains on likelihood only).  One encoder pass; without gradient the device prefix beam search (`nbest` entries per
+        utterance) on the CTC logits and every entry's error count against the transcript; then the entries' exact CTC
+        log-likelihoods (ops.ctc_nbest_logp, differentiable), renormalised over the list:
+            loss = mean_b sum_n P_n (W_n - mean W) + ce_weight * (the joint loss of forward()).
+        Entries that do not exist or have no alignment (logp = -inf) take no part.  Eager only; no host read.
+        nbest_lists: (prefixes (B * nbest, T') int, lengths (B * nbest) int) to score instead of searching.
+        -> loss, info: device tensors loss_mwer, loss_base, acc (None with ctc_weight == 1), expected_errors (B), logp (B, nbest),
+        errors (B, nbest), prefixes (B * nbest, T') int32, plen (B * nbest) int32.  Needs the device beam and nbest <= 16
+        (ValueError otherwise: there is no host implementation)."""
+        from openeat_amd.utils.mwer import mwer_loss
+        assert targets_length.dim() == 1, targets_length.shape
+        assert (features.shape[0] == features_length.shape[0] == targets.shape[0] == targets_length.shape[0]), \
+            (features.shape, features_length.shape, targets.shape, targets_length.shape)
+        spec = hip.PrefixSearch(int(nbest))
+        spec.validate("forward_mwer", DEVICE_BEAM)
+        nbest = spec.beam
+        ops.predrop_clear()
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        logits = self.ctc.logits(encoder_out)
+        B, T = logits.shape[0], logits.shape[1]
+        with torch.no_grad():
+            if nbest_lists is None:
+                top_p, top_i = ops.topk_rows(logits.detach(), nbest, log_softmax=True)
+                r = hip._prefix_beam_device("forward_mwer", top_p, top_i, encoder_out_lens.to(torch.int32), spec, True)
+                prefixes, plen = r.prefixes.view(B * nbest, -1), r.plen.view(B * nbest)
+            else:
+                prefixes, plen = nbest_lists
+            counts = ops.edit_distance(targets, targets_length, prefixes[:, :EDIT_DISTANCE_MAX], plen, group=nbest)
+            errors = counts[:, 1:].sum(1).view(B, nbest)
+        logp = ops.ctc_nbest_logp(logits, encoder_out_lens, prefixes[:, :min(T, 255)], plen, nbest)
+        exists = torch.isfinite(logp.detach())
+        per_utt, expected = mwer_loss(logp, errors.to(logp.dtype), exists)
+        loss_mwer = per_utt.mean()
+        loss_ctc = self.ctc(encoder_out, encoder_out_lens, targets, targets_length)
+        acc = None
+        if self.ctc_weight < 1:
+            l_loss, r_loss, acc = self._att_losses(encoder_out, encoder_mask, targets, targets_length)
+            base = self._joint_loss(loss_ctc, l_loss, r_loss)
+        else:
+            base = loss_ctc
+        loss = loss_mwer + ce_weight * base
+        return loss, dict(loss_mwer=loss_mwer.detach(), loss_base=base.detach(), acc=acc, expected_errors=expected.detach(),
+                          logp=logp.detach(), errors=errors, prefixes=prefixes, plen=plen)
+
+    @torch.no_grad()
+    def ctc_nbest(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int):
+        """The CTC n-best list of every utterance with each entry's EXACT CTC log-likelihood beside the beam's score (which
+        sums only the alignments that survived the pruning, so exact >= beam up to rounding): per utterance
+        [(tokens tuple, beam_score, exact_logp)] in the beam's order.  Device beam only (ValueError otherwise)."""
+        assert features.shape[0] == features_length.shape[0]
+        spec = hip.PrefixSearch(int(beam_size))
+        spec.validate("ctc_nbest", DEVICE_BEAM)
+        encoder_out, encoder_mask, pre, plen, scores, bad, _ = self._rescore_stage1(features, features_length, spec)
+        B, T = encoder_out.shape[0], encoder_out.shape[1]
+        exact = ops.ctc_nbest_logp(self.ctc.logits(encoder_out), encoder_mask.squeeze(1).sum(1), pre[:, :min(T, 255)], plen, spec.beam)
+        lists = hip._nbest_lists(pre.view(B, spec.beam, -1), plen.view(B, spec.beam), scores.view(B, spec.beam), exact)
+        hip.check_prefix_beam_status(bad, "ctc_nbest")            # (the copies above have drained the stream)
+        return lists
+
     def _joint_loss(self, loss_ctc, l_loss, r_loss):
         """asr_model.py:150-157 with :196-198 folded in: ctc_weight * ctc + (1 - ctc_weight) * (l * (1 - rw) + r * rw)."""
         if l_loss.is_cuda and l_loss.dtype == torch.float32:

@@ -2521,6 +2521,69 @@ def edit_distance(ref, ref_lens, hyp, hyp_lens, group: int = 1, align: bool = Fa
     return (counts, r2h) if align else counts
 
 
+class CTCNbestFn(torch.autograd.Function):
+    """oe_ctc_nbest_score / oe_ctc_nbest_grad (semantics in include/openeat_hip.h): the exact CTC log-likelihood of each of
+    `group` hypotheses per utterance, differentiable with respect to the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, hlens, hyps, hyp_lens, group):
+        B, T, V = (int(s) for s in logits.shape)
+        Vp = _vpad(V)
+        # rows padded to whole float4s, as CTCHeadFn's logits are: a view of such a buffer is taken as it is
+        if logits.stride(2) == 1 and logits.stride(1) == Vp and logits.stride(0) == T * Vp and logits.data_ptr() % 16 == 0:
+            buf = logits
+        else:
+            buf = _new(B, T, Vp, like=logits, zero=(Vp != V))
+            buf[..., :V].copy_(logits)
+        Lmax = int(hyps.shape[1])
+        hyp32 = hyps.to(torch.int32).contiguous()
+        hl32, len32 = hlens.to(torch.int32).contiguous(), hyp_lens.to(torch.int32).contiguous()
+        dev = logits.device
+        lib = hip.lib()
+        ws = torch.empty(lib.oe_ctc_nbest_workspace_bytes(B, T, group, Lmax), dtype=torch.uint8, device=dev)
+        saved = None
+        if ctx.needs_input_grad[0]:
+            saved = torch.empty(lib.oe_ctc_nbest_saved_bytes(B, T, group, Lmax), dtype=torch.uint8, device=dev)
+        logp = _new(B * group, like=logits)
+        hip.call("oe_ctc_nbest_score", buf, Vp, B, T, V, hl32, hyp32 if Lmax else None, Lmax, len32, group, Lmax, logp, saved, ws)
+        if saved is not None:
+            ctx.save_for_backward(buf, hl32, hyp32, len32, logp, saved)
+            ctx.cfg = (B, T, V, Vp, group, Lmax)
+        return logp.view(B, group)
+
+    @staticmethod
+    def backward(ctx, g):
+        buf, hl32, hyp32, len32, logp, saved = ctx.saved_tensors
+        B, T, V, Vp, group, Lmax = ctx.cfg
+        g = _chk(g, "ctc_nbest_logp gradient")
+        dlogits = _new(B, T, Vp, like=buf)
+        hip.call("oe_ctc_nbest_grad", buf, Vp, B, T, V, hl32, hyp32 if Lmax else None, Lmax, len32, group, Lmax, logp, g, saved,
+                 dlogits, None)
+        return dlogits[..., :V], None, None, None, None
+
+
+def ctc_nbest_logp(logits, hlens, hyps, hyp_lens, group: int):
+    """Exact CTC log-likelihood of an n-best list: logits (B, T, V) float32 (raw, not normalised), hlens (B) valid frames,
+    hyps (B * group, Lmax <= 255) token ids of which hyp_lens (B * group) count (< 0: the slot does not exist), all on the
+    device -> logp (B, group) float32, -inf for an infeasible row (the rule is in include/openeat_hip.h).  Differentiable
+    with respect to the logits (one launch in backward); hyps and the lengths are not.  No host read: capturable."""
+    ts = (logits, hlens, hyps, hyp_lens)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError("ctc_nbest_logp: openeat_amd ops need CUDA tensors; there is no CPU fallback")
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise TypeError(f"ctc_nbest_logp: logits must be a float32 (B, T, V) tensor (got {logits.dtype}, {tuple(logits.shape)})")
+    group = int(group)
+    B = int(logits.shape[0])
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ts[1:]) or hyps.dim() != 2 or hlens.shape != (B,) \
+            or hyp_lens.shape != hyps.shape[:1]:
+        raise TypeError("ctc_nbest_logp: hlens (B), hyps (B * group, Lmax) and hyp_lens (B * group) must be integer tensors")
+    if not 1 <= group <= 64 or hyps.shape[0] != B * group:
+        raise ValueError(f"ctc_nbest_logp: {B} utterances x group {group} (1..64) != {hyps.shape[0]} hypotheses")
+    if hyps.shape[1] > 255:
+        raise ValueError(f"ctc_nbest_logp: hypotheses are {hyps.shape[1]} tokens wide; the limit is 255")
+    return CTCNbestFn.apply(logits, hlens, hyps, hyp_lens, group)
+
+
 def _prefix_score_logp(name, logp, lens, group):
     if not (isinstance(logp, torch.Tensor) and logp.is_cuda) or not (lens is None or (isinstance(lens, torch.Tensor) and lens.is_cuda)):
         raise TypeError(f"{name}: openeat_amd ops need CUDA tensors; there is no CPU fallback")

@@ -21,6 +21,7 @@ class Executor:
         clip = args.get("grad_clip", 5.0)
         accum_grad = args.get("accum_grad", 1)
         reducer = args.get("grad_reducer", None)          # openeat_amd.ddp.GradAllReduce for data parallel runs
+        mwer = args.get("mwer")                           # a dict of ASRModel.forward_mwer keyword arguments, or absent
         fused = isinstance(optimizer, FusedAdam)
         if fused:
             optimizer.max_grad_norm = clip
@@ -53,7 +54,12 @@ class Executor:
             boundary = batch_idx % accum_grad == 0
             if reducer is not None:
                 reducer.overlap_enabled = boundary           # model.no_sync on the micro-steps in between (executor.py:42-45)
-            loss, acc = model(**batch)
+            if mwer is not None:
+                # minimum word error rate training over the model's own n-best lists (ASRModel.forward_mwer)
+                loss, info = model.forward_mwer(**batch, **mwer)
+                acc = info["acc"]
+            else:
+                loss, acc = model(**batch)
             loss = torch.mean(loss) / accum_grad
             acc = None if acc is None else torch.mean(acc)
             if torch.isfinite(loss):
@@ -80,6 +86,8 @@ class Executor:
                     batch_idx, n_batches, loss.item() * accum_grad, total_loss / max(num_seen_utts, 1))
                 if acc is not None:
                     msg += "Acc:{:.4f} AAcc:{:.4f} ".format(acc.item(), total_acc / max(num_seen_utts, 1))
+                if mwer is not None:
+                    msg += "MWER:{:.4f} ExpErr:{:.4f} ".format(info["loss_mwer"].item(), info["expected_errors"].mean().item())
                 logger.info(msg + "lr:{:.8f} rank:{}".format(lr, local_rank))
         return total_loss / max(num_seen_utts, 1), total_acc / max(num_seen_utts, 1)
 
