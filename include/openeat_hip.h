@@ -369,7 +369,17 @@ int oe_layernorm_bwd_dx_drop_pl(const float* dy, const float* x, const float* ga
  *   out: nll (B) unweighted, infeasible -> 0;  loss_sum[0] = sum_b w_b * nll_b,
  *        dlogits (B, T, ldv) = grad_scale * d loss_sum / d logits (may alias
  *        logits; padded frames / infeasible utterances exactly 0), or NULL.
+ *        Columns >= V of dlogits (the row padding) are never written.
  *   workspace: float[ oe_ctc_workspace_floats(B,T,Lmax) ].
+ *   Two paths, chosen by the launch's T alone (every utterance of a launch takes the same one):
+ *     T <= 248: alpha / beta / ll in float32.  The error of an occupancy grows with the utterance's negative
+ *        log-likelihood; against a float64 loss the gradient holds rtol 2e-3 / atol 2e-5 * grad_scale * w_b up to
+ *        |nll| ~ 2000 nats (measured: 0.7 of that tolerance at T = 248, V = 3246, untrained posteriors).  The launch forms
+ *        of oe_ctc_config apply here.
+ *     T  > 248: alpha / beta / ll in float64 (the recursion of oe_ctc_nbest_score), rows, alpha/beta, labels one after the
+ *        other whatever oe_ctc_config says.  The same tolerance holds with a margin of 10x or more up to T = 2000 and
+ *        |nll| ~ 22000 nats (tests/test_ctc_long_gpu.py).  The workspace grows by the two float64 trellises.
+ *     Both: nll rtol 1e-4 / atol 1e-3; loss-only calls, in-place gradients, utt_weight, zero_infinity and graph capture.
  * ------------------------------------------------------------------------- */
 size_t oe_ctc_workspace_floats(int B, int T, int Lmax);
 /* oe_ctc_loss_fused launch form, for tests and tuning tools (-1 / 0 keeps a value): pipe_mode 0 = rows, alpha/beta, labels one

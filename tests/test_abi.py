@@ -62,6 +62,22 @@ def test_ctypes_structures_have_the_layout_the_header_declares(tmp_path):
     print(f"{len(classes)} structs, {len(want)} sizes and offsets agree: {', '.join(sorted(c_names.values()))}")
 
 
+def test_ctc_workspace_covers_both_state_widths():
+    """oe_ctc_loss_fused keeps alpha / beta / ll in float32 for launches of T <= 248 frames (the bench's length; the size
+    every earlier caller allocated) and in float64 above (include/openeat_hip.h): there the workspace holds lp in float32,
+    the label chains, and ll and two trellises as 8-byte aligned doubles."""
+    lib = ctypes.CDLL(LIB)
+    lib.oe_ctc_workspace_floats.restype = ctypes.c_size_t
+    lib.oe_ctc_workspace_floats.argtypes = [ctypes.c_int] * 3
+    for B, T, Lmax in ((32, 248, 40), (1, 1, 0), (3, 131, 255)):
+        Sp = 2 * Lmax + 1
+        assert lib.oe_ctc_workspace_floats(B, T, Lmax) == B + 3 * B * T * Sp + B * Sp + 16 + 2 * B * T + 2
+    for B, T, Lmax in ((2, 249, 7), (2, 1500, 200), (1, 2000, 255)):
+        Sp = 2 * Lmax + 1
+        need = B + B * T * Sp + B * Sp + 1 + 2 * (B + 2 * B * T * Sp + 2)
+        assert lib.oe_ctc_workspace_floats(B, T, Lmax) >= need
+
+
 def test_invalid_arguments_are_reported_not_launched():
     from openeat_amd import hip
     lib = hip.lib()

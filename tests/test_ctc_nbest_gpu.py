@@ -173,8 +173,17 @@ def test_shapes_where_a_mechanism_changes(shape, lo, hi):
 
 def test_group_of_one_is_the_fused_ctc_loss():
     """group = 1: logp = -nll of oe_ctc_loss_fused within 1e-3, and with g = -1 dlogits is the loss's gradient."""
-    B, T, V, ldv, Lmax = 3, 50, 29, 32, 12
-    c = _random_case(B, 1, T, V, ldv, Lmax, [50, 31, 17], 51, 3, 12, missing=False)
+    _group_of_one((3, 50, 29, 32, 12), [50, 31, 17], 3, 12)
+
+
+def test_group_of_one_is_the_fused_ctc_loss_at_a_long_utterance():
+    """(B, T, V, ldv, Lmax) = (2, 1500, 64, 64, 200): |nll| in the thousands, the same bounds."""
+    _group_of_one((2, 1500, 64, 64, 200), [1500, 700], 150, 200)
+
+
+def _group_of_one(shape, hlens, lo, hi):
+    B, T, V, ldv, Lmax = shape
+    c = _random_case(B, 1, T, V, ldv, Lmax, hlens, 51, lo, hi, missing=False)
     g = torch.full((B,), -1.0)
     logp, dl = _device_run(c, g=g)
     buf = torch.full((B, T, ldv), 0.25, device=DEV)

@@ -5,6 +5,7 @@ Tolerances (fp32 kernels; the MFMA GEMM is exact-fp32 products with a
 different summation order than aten): rtol 1e-4 / atol scaled to the data.
 """
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -292,9 +293,7 @@ def test_ctc_golden_f07(ctc_form):
     assert torch.all(dl[2] == 0) and torch.all(dl[1, 9:] == 0)       # exact zeros, as the reference
 
 
-@pytest.mark.parametrize("B,T,V,Lmax,ldv", [(6, 50, 37, 9, 40), (4, 120, 3246, 40, 3248), (3, 90, 501, 70, 504),
-                                             (2, 300, 100, 140, 100)])
-def test_ctc_vs_oracle(B, T, V, Lmax, ldv, ctc_form):
+def _ctc_vs_oracle_inputs(B, T, V, Lmax):
     torch.manual_seed(7)
     logits = torch.randn(B, T, V) * 2
     hl = torch.randint(T // 2, T + 1, (B,))
@@ -302,6 +301,23 @@ def test_ctc_vs_oracle(B, T, V, Lmax, ldv, ctc_form):
     yl = torch.randint(1, Lmax + 1, (B,))
     yl[-1] = Lmax
     ys = torch.randint(1, V, (B, Lmax))
+    return logits, hl, yl, ys
+
+
+@functools.lru_cache(maxsize=None)
+def _ctc_float64(B, T, V, Lmax):
+    """torch's CTC loss in float64 on the float32 logits of test_ctc_vs_oracle -> (nll (B), d sum nll / d logits); once per shape."""
+    logits, hl, yl, ys = _ctc_vs_oracle_inputs(B, T, V, Lmax)
+    lg = logits.double().requires_grad_()
+    per = F.ctc_loss(lg.transpose(0, 1).log_softmax(2), ys, hl, yl, reduction="none", zero_infinity=True)
+    per.sum().backward()
+    return per.detach(), lg.grad
+
+
+@pytest.mark.parametrize("B,T,V,Lmax,ldv", [(6, 50, 37, 9, 40), (4, 120, 3246, 40, 3248), (3, 90, 501, 70, 504),
+                                             (2, 300, 100, 140, 100)])
+def test_ctc_vs_oracle(B, T, V, Lmax, ldv, ctc_form):
+    logits, hl, yl, ys = _ctc_vs_oracle_inputs(B, T, V, Lmax)
     lg = logits.clone().requires_grad_()
     logp = lg.transpose(0, 1).log_softmax(2)
     per = F.ctc_loss(logp, ys, hl, yl, reduction="none", zero_infinity=True)
@@ -310,6 +326,11 @@ def test_ctc_vs_oracle(B, T, V, Lmax, ldv, ctc_form):
     torch.testing.assert_close(nll, per.detach(), rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(tot[0], per.sum().detach(), rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(dl, lg.grad, rtol=2e-3, atol=2e-5)
+    # torch's loss in float64 (its float32 loss above drifts with |nll| as a float32 kernel does): same tolerances
+    n64, g64 = _ctc_float64(B, T, V, Lmax)
+    torch.testing.assert_close(nll.double(), n64, rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(tot[0].double(), n64.sum(), rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(dl.double(), g64, rtol=2e-3, atol=2e-5)
     if B * T * V < 50000:   # third opinion: float64 loop-level alpha/beta
         n2, g2 = ctc_np.ctc_nll_and_grad(logits.numpy(), hl.numpy(), ys.numpy(), yl.numpy())
         np.testing.assert_allclose(nll.numpy(), n2, rtol=1e-4, atol=1e-3)
