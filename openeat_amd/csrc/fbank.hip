@@ -21,6 +21,12 @@
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        \
         __builtin_amdgcn_wave_barrier();                          \
     } while (0)
+// log(x) as log2(x) * ln 2 with the product in double.  The compiler's float32 expansion of log ends in a compensated sum
+// r + t (r = y * c, t = fma(y, cc, fma(y, c, -r)), c + cc = ln 2); with contraction allowed it becomes fma(y, c, t), the residual
+// of r's rounding counts twice and the result is up to 1 ulp off - also at FLT_EPSILON, the floor every silent frame sits on:
+// the kernel gave -15.9423857 where log(2^-23) rounds to -15.9423847.  One double product per mel bin and frame.
+__device__ __forceinline__ float fb_log(float x) { return (float)((double)log2f(x) * 0.6931471805599453); }
+
 template <int FB_NFFT>
 __global__ __launch_bounds__(64 * FB_WAVES) void fbank_kernel(const float* __restrict__ wav, const int* __restrict__ nsamples,
                                                               int B, long wav_stride, int Tmax, int win, int hop, int n_mel,
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(64 * FB_WAVES) void fbank_kernel(const float* __res
             const int st = mel_start[m], o0 = mel_off[m], o1 = mel_off[m + 1];
             float acc = 0.f;
             for (int q = o0; q < o1; ++q) acc += mel_w[q] * s1[st + (q - o0)].x;
-            r = __logf(fmaxf(acc, floor_eps));
+            r = fb_log(fmaxf(acc, floor_eps));
             if (cmvn_mean) r = (r - cmvn_mean[m]) * cmvn_istd[m];
         }
         dst[m] = r;      // frames past the utterance end are zero, like pad_sequence (dataset.py:217)

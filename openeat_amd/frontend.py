@@ -64,6 +64,8 @@ class Fbank:
             out = torch.empty(B, T, self.n_mel, device=wav.device)
         ns = None if nsamples is None else nsamples.to(torch.int32).contiguous()
         mean, istd = (None, None) if cmvn is None else cmvn
+        if T == 0:                                                  # a batch shorter than one window: nothing to launch
+            return out, torch.zeros(B, dtype=torch.int32, device=wav.device)
         if dither != 0.0:
             hip.call("oe_fbank_dither", wav, ns, B, N, T, self.win, self.hop, self.n_mel, self.scale, self.preemph, self.window,
                      self.twiddle, self.mel_start, self.mel_off, self.mel_w, FLT_EPS, mean, istd, float(dither), int(seed), out)
