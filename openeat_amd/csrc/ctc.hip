@@ -48,9 +48,8 @@ __global__ __launch_bounds__(256) void ctc_rows_kernel(const float* logits, long
                                                         const int* __restrict__ hlens, const int* __restrict__ targets,
                                                         int Lmax, const int* __restrict__ tlens, int Sp, float scale,
                                                         const float* __restrict__ utt_weight, float* __restrict__ lp_out,
-                                                        float* dlogits, int t0, int Tc, float2* __restrict__ rowstat) {
+                                                        float* dlogits, int t0, int Tc) {
     // frames t0 .. t0 + Tc - 1 of every utterance (`rows` = B * Tc of them; the whole batch: t0 = 0, Tc = T)
-    // rowstat (optional): (row maximum, 1 / sum exp(x - max)) of every live row, for ctc_dense_row
     const int lane = threadIdx.x & 63;
     const long rloc = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (rloc >= rows) return;
@@ -136,127 +135,6 @@ __global__ __launch_bounds__(256) void ctc_rows_kernel(const float* logits, long
         const int st = lane + 64 * q;
         if (st < S) lp_out[row * Sp + st] = (lv[q] - m) * 1.4426950408889634f - l2s;
     }
-    if (rowstat && lane == 0) rowstat[row] = make_float2(m, __builtin_amdgcn_exp2f(-l2s));
-}
-
-// ---- the overlapped form (oe_ctc_loss_fused, ctc_pipe_mode 3 / 4) ---------------------------------------------------------
-// One after the other the three passes cost rows + chain + labels (116 + 60 + 30 us at B = 64 x 16 s): the recursion is a serial
-// chain on 64 waves and the label fix-up a latency-bound scatter, both with the chip idle around them.  Here the row statistics
-// come first (from the logits: ctc_rows_kernel<.., false> with `rowstat`, a read-only pass; or from the per-32-column partials
-// the projection GEMM's epilogue left: ctc_lp_kernel, a few microseconds), and then TWO launches of mixed blocks follow:
-//   launch 2: one block per utterance runs alpha / beta / the label chains  +  dense-gradient blocks for frames [0, T/2)
-//   launch 3: the label fix-up blocks of all frames                         +  dense-gradient blocks for frames [T/2, T)
-// The special blocks come first in the grid (dispatched first), the dense blocks - pure streaming - fill the chip around them.
-// No block waits for another: the dense blocks write every column EXCEPT the blank and the utterance's labels (a per-wave bitmask
-// in LDS), the fix-up blocks write exactly those, so the two kinds never touch the same word and need no order between them
-// (in place too: a dense wave may read a label column the fix-up has already overwritten, but it never uses or writes it).
-// Rows of infeasible utterances are zeroed by a last small launch (ctc_final_kernel), which also sums the loss.
-template <int NV4>
-__device__ __forceinline__ void ctc_dense_row(const float* logits, long ldv, long rows, int T, int V, const int* __restrict__ hlens,
-                                              const int* __restrict__ targets, int Lmax, const int* __restrict__ tlens, float scale,
-                                              const float* __restrict__ utt_weight, const float2* __restrict__ rowstat, float* dlogits,
-                                              int t0, int Tc, long rloc, unsigned* maskw) {
-    constexpr int MW = NV4 * 8;                        // bitmask dwords: 256 * NV4 columns
-    const int lane = threadIdx.x & 63;
-    if (rloc >= rows) return;
-    const int b = (int)(rloc / Tc), t = t0 + (int)(rloc % Tc);
-    const long row = (long)b * T + t;
-    const float* p = logits + row * ldv;
-    float* g = dlogits + row * ldv;
-    const int nv = (V + 3) >> 2;
-    if (t >= hlens[b]) {                               // padded frame: exact zeros in every column
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = lane; i < nv; i += 64) ctc_store4(g, 4 * i, V, z);
-        return;
-    }
-    float4 v[NV4];
-    const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-    for (int j = 0; j < NV4; ++j) {
-        const int i = lane + 64 * j;
-        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < nv) v[j] = p4[i];
-    }
-    const float2 st = rowstat[row];
-    if (utt_weight) scale *= utt_weight[b];
-    // the columns the fix-up owns: blank and the utterance's labels
-#pragma unroll
-    for (int i = lane; i < MW; i += 64) maskw[i] = (i == 0) ? 1u : 0u;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const int L = min(tlens[b], Lmax);
-    for (int i = lane; i < L; i += 64) {
-        const int c = targets[(long)b * Lmax + i];
-        if (c >= 0 && c < V) atomicOr(&maskw[c >> 5], 1u << (c & 31));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    const float f = scale * st.y;
-#pragma unroll
-    for (int j = 0; j < NV4; ++j) {
-        const int i = lane + 64 * j;
-        if (i < nv) {
-            const int e = 4 * i;
-            unsigned bits = (maskw[e >> 5] >> (e & 31)) & 0xfu;
-            if (e + 3 >= V) bits |= (0xfu << (V - e)) & 0xfu;     // the row padding is nobody's: never written
-            const float4 o = make_float4(__expf(v[j].x - st.x) * f, __expf(v[j].y - st.x) * f, __expf(v[j].z - st.x) * f, __expf(v[j].w - st.x) * f);
-            if (bits == 0u) {
-                reinterpret_cast<float4*>(g)[i] = o;
-            } else {
-                if (!(bits & 1u)) g[e] = o.x;
-                if (!(bits & 2u)) g[e + 1] = o.y;
-                if (!(bits & 4u)) g[e + 2] = o.z;
-                if (!(bits & 8u)) g[e + 3] = o.w;
-            }
-        }
-    }
-}
-
-// Row statistics from the projection GEMM's epilogue (oe_gemm_args.row_stats: per row and per group of 32 columns the pair
-// (max, sum exp(x - max))) -> lp at the states and (row maximum, 1 / sum): one wave per frame, no pass over the logits.
-__global__ __launch_bounds__(256) void ctc_lp_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                      const int* __restrict__ hlens, const int* __restrict__ targets, int Lmax,
-                                                      const int* __restrict__ tlens, int Sp, const float2* __restrict__ part, int groups,
-                                                      float* __restrict__ lp_out, float2* __restrict__ rowstat) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    const int L = min(tlens[b], Lmax);
-    const int S = 2 * L + 1;
-    float lv[CTC_MAXQ];
-#pragma unroll
-    for (int q = 0; q < CTC_MAXQ; ++q) {
-        const int st = lane + 64 * q;
-        lv[q] = 0.f;
-        if (st < S) lv[q] = p[(st & 1) ? targets[(long)b * Lmax + (st >> 1)] : 0];
-    }
-    float m = NEG_INF;
-    const float2* pr = part + row * groups;
-    float2 mine[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int gidx = lane + 64 * k;
-        mine[k] = make_float2(NEG_INF, 0.f);
-        if (gidx < groups) mine[k] = pr[gidx];
-        m = fmaxf(m, mine[k].x);
-    }
-    for (int gidx = lane + 256; gidx < groups; gidx += 64) m = fmaxf(m, pr[gidx].x);
-    m = wave_max(m);
-    float ssum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) if (mine[k].y > 0.f) ssum += mine[k].y * __expf(mine[k].x - m);
-    for (int gidx = lane + 256; gidx < groups; gidx += 64) { const float2 q2 = pr[gidx]; if (q2.y > 0.f) ssum += q2.y * __expf(q2.x - m); }
-    ssum = wave_sum(ssum);
-    const float l2s = __builtin_amdgcn_logf(ssum);
-#pragma unroll
-    for (int q = 0; q < CTC_MAXQ; ++q) {
-        const int st = lane + 64 * q;
-        if (st < S) lp_out[row * Sp + st] = (lv[q] - m) * 1.4426950408889634f - l2s;
-    }
-    if (lane == 0) rowstat[row] = make_float2(m, 1.f / ssum);
 }
 
 // ------------------------------------------------------------------ k2 ------
@@ -406,17 +284,29 @@ __device__ __forceinline__ void ctc_recurse(int lane, int Tb, int S, int Sp, con
     }
 }
 
-// One block per utterance: wave 0 runs alpha, wave 1 beta, and wave 2 meanwhile links the states that share a class (a
-// label occurring more than once in the target), once per utterance: chain[b][s] for odd s = (next state with the same
-// label, + 1; 0 = none) | (first of its label ? 1 << 16 : 0).  k3 follows these chains per frame instead of comparing
-// labels (that comparison was O(S^2) per frame).
+// chain[b][s] for odd s = (next state with the same label, + 1; 0 = none) | (first of its label ? 1 << 16 : 0): the states
+// that share a class (a label occurring more than once in the target), linked once per utterance by one wave.  k3 follows
+// these chains per frame instead of comparing labels (that comparison was O(S^2) per frame).
+__device__ __forceinline__ void ctc_link_chains(int lane, int S, const int* __restrict__ tg, int* __restrict__ chain_b) {
+    for (int s = 1 + 2 * lane; s < S; s += 128) {
+        const int c = tg[s >> 1];
+        int head = 1, nx = 0;
+        for (int q = 1; q < s; q += 2) if (tg[q >> 1] == c) { head = 0; break; }
+        for (int q = s + 2; q < S; q += 2) if (tg[q >> 1] == c) { nx = q + 1; break; }
+        chain_b[s] = nx | (head << 16);
+    }
+}
+
+// One block of three waves per utterance: wave 0 runs alpha, wave 1 beta, and wave 2 meanwhile links the label chains.
 template <int NS, int CH>
-__device__ __forceinline__ void ctc_alphabeta_block(int b, float* fin, int T, const int* __restrict__ hlens, const int* __restrict__ targets,
-                                                    int Lmax, const int* __restrict__ tlens, int Sp,
-                                                    const float* __restrict__ lp, float* __restrict__ alpha,
-                                                    float* __restrict__ beta, float* __restrict__ ll_out,
-                                                    float* __restrict__ nll_out, int* __restrict__ chain,
-                                                    float* __restrict__ dump) {
+__global__ __launch_bounds__(192) void ctc_alphabeta_kernel(int T, const int* __restrict__ hlens, const int* __restrict__ targets,
+                                                            int Lmax, const int* __restrict__ tlens, int Sp,
+                                                            const float* __restrict__ lp, float* __restrict__ alpha,
+                                                            float* __restrict__ beta, float* __restrict__ ll_out,
+                                                            float* __restrict__ nll_out, int* __restrict__ chain,
+                                                            float* __restrict__ dump) {
+    __shared__ float fin[2];
+    const int b = blockIdx.x;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int Tb = min(hlens[b], T);
@@ -426,14 +316,8 @@ __device__ __forceinline__ void ctc_alphabeta_block(int b, float* fin, int T, co
     if (threadIdx.x < 2) fin[threadIdx.x] = CTC_NEG;
     __syncthreads();
     if (wv == 2) {
-        for (int s = 1 + 2 * lane; s < S; s += 128) {
-            const int c = tg[s >> 1];
-            int head = 1, nx = 0;
-            for (int q = 1; q < s; q += 2) if (tg[q >> 1] == c) { head = 0; break; }
-            for (int q = s + 2; q < S; q += 2) if (tg[q >> 1] == c) { nx = q + 1; break; }
-            chain[(long)b * Sp + s] = nx | (head << 16);
-        }
-    } else if (Tb > 0 && wv < 2) {       // (a fourth wave - the mixed launch's 256-thread blocks - only keeps the barriers company)
+        ctc_link_chains(lane, S, tg, chain + (long)b * Sp);
+    } else if (Tb > 0 && wv < 2) {      // (wv < 2 always holds in a block of three waves)
         float a[NS];
         if (wv == 0) {
             ctc_recurse<true, NS, CH>(lane, Tb, S, Sp, tg, lp + base, alpha + base, dump, a, 0, Tb);
@@ -459,35 +343,6 @@ __device__ __forceinline__ void ctc_alphabeta_block(int b, float* fin, int T, co
         ll_out[b] = ll;                                        // base 2, for k3
         nll_out[b] = (ll == NEG_INF) ? 0.f : -ll * CTC_LN2;
     }
-}
-template <int NS, int CH>
-__global__ __launch_bounds__(192) void ctc_alphabeta_kernel(int T, const int* __restrict__ hlens, const int* __restrict__ targets,
-                                                            int Lmax, const int* __restrict__ tlens, int Sp,
-                                                            const float* __restrict__ lp, float* __restrict__ alpha,
-                                                            float* __restrict__ beta, float* __restrict__ ll_out,
-                                                            float* __restrict__ nll_out, int* __restrict__ chain,
-                                                            float* __restrict__ dump) {
-    __shared__ float fin[2];
-    ctc_alphabeta_block<NS, CH>(blockIdx.x, fin, T, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_out, nll_out, chain, dump);
-}
-// overlapped form, launch 2: blocks 0 .. B-1 = the recursion of one utterance each (waves 0 - 2 of four), the rest = dense rows
-template <int NV4, int NS, int CH>
-__global__ __launch_bounds__(256) void ctc_chain_dense_kernel(int B, const float* logits, long ldv, int T, int V, const int* __restrict__ hlens,
-                                                              const int* __restrict__ targets, int Lmax, const int* __restrict__ tlens,
-                                                              int Sp, const float* __restrict__ lp, float* __restrict__ alpha,
-                                                              float* __restrict__ beta, float* __restrict__ ll_out, float* __restrict__ nll_out,
-                                                              int* __restrict__ chain, float* __restrict__ dump, float scale,
-                                                              const float* __restrict__ utt_weight, const float2* __restrict__ rowstat,
-                                                              float* dlogits, int t0, int Tc) {
-    __shared__ float fin[2];
-    __shared__ unsigned maskw[4][NV4 * 8];
-    if ((int)blockIdx.x < B) {
-        ctc_alphabeta_block<NS, CH>(blockIdx.x, fin, T, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_out, nll_out, chain, dump);
-        return;
-    }
-    const int wv = threadIdx.x >> 6;
-    ctc_dense_row<NV4>(logits, ldv, (long)B * Tc, T, V, hlens, targets, Lmax, tlens, scale, utt_weight, rowstat, dlogits, t0, Tc,
-                       ((long)blockIdx.x - B) * 4 + wv, maskw[wv]);
 }
 
 // ---- the pipelined form (oe_ctc_loss_fused with T >= CTC_PIPE_MIN_T): the recursion in time chunks, one direction per launch.
@@ -536,24 +391,15 @@ __global__ __launch_bounds__(64) void ctc_chain_kernel(const int* __restrict__ t
                                                        int* __restrict__ chain) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int S = 2 * min(tlens[b], Lmax) + 1;
-    const int* tg = targets + (long)b * Lmax;
-    for (int s = 1 + 2 * lane; s < S; s += 128) {
-        const int c = tg[s >> 1];
-        int head = 1, nx = 0;
-        for (int q = 1; q < s; q += 2) if (tg[q >> 1] == c) { head = 0; break; }
-        for (int q = s + 2; q < S; q += 2) if (tg[q >> 1] == c) { nx = q + 1; break; }
-        chain[(long)b * Sp + s] = nx | (head << 16);
-    }
+    ctc_link_chains(lane, S, targets + (long)b * Lmax, chain + (long)b * Sp);
 }
 
 // ------------------------------------------------------------------ k3 ------
 // One wave per frame (four per block).  k1 has written softmax * scale everywhere; the classes of the target get their
 // occupation term here, and frames of an infeasible utterance (ll = -inf) are zeroed.  Block 0 also sums the loss.
 // Sums run in a fixed order (blank: per-lane partials + shuffle tree; a label: along its chain): deterministic.
-// ZERO_INF: rows of infeasible utterances are zeroed here (the three-launch form; the overlapped form leaves that to
-// ctc_final_kernel, because its dense blocks write those rows at the same time)
 // ST: the type of alpha, beta and ll - float, or double on the long-launch path, where the exponent is formed in float64
-template <bool ZERO_INF, typename ST = float>
+template <typename ST>
 __device__ __forceinline__ void ctc_labels_block(float* sh, long blk, long rows, int B, int T, int V, long ldv, const int* __restrict__ hlens,
                                                  const int* __restrict__ targets, int Lmax, const int* __restrict__ tlens,
                                                  int Sp, const float* __restrict__ lp, const ST* __restrict__ alpha,
@@ -576,7 +422,7 @@ __device__ __forceinline__ void ctc_labels_block(float* sh, long blk, long rows,
     const bool frame = inrange && t < hlens[b];
     const ST ll = ll_in[b];
     float* g = dlogits + row * ldv;
-    if (ZERO_INF && frame && ll == NEG_INF) {
+    if (frame && ll == NEG_INF) {
         for (int i = lane; i < V; i += 64) g[i] = 0.f;
     }
     const bool live = frame && ll != NEG_INF;
@@ -622,8 +468,8 @@ __global__ __launch_bounds__(256) void ctc_labels_kernel(long rows, int B, int T
                                                           float scale, const float* __restrict__ utt_weight,
                                                           float* __restrict__ dlogits, float* __restrict__ loss_sum, int t0, int Tc) {
     extern __shared__ __attribute__((aligned(16))) float sh[];   // per wave: gam[Sp]
-    ctc_labels_block<true>(sh, blockIdx.x, rows, B, T, V, ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_in, chain, nll, scale,
-                           utt_weight, dlogits, loss_sum, t0, Tc);
+    ctc_labels_block<float>(sh, blockIdx.x, rows, B, T, V, ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_in, chain, nll, scale,
+                            utt_weight, dlogits, loss_sum, t0, Tc);
 }
 // ---- the float64-state path (launches with T > ctc_f32_max_t, see there): k1 as above, then k2 / k3 with alpha, beta and ll in
 // float64.  The recursion is ctc_f64.h's (the n-best scorer's); the exponent of an occupancy is formed in float64, so its error
@@ -646,13 +492,7 @@ __global__ __launch_bounds__(192) void ctc_alphabeta_f64_kernel(int T, const int
     if (threadIdx.x < 2) fin[threadIdx.x] = NB_NEG_D;
     __syncthreads();
     if (wv == 2) {
-        for (int s = 1 + 2 * lane; s < S; s += 128) {
-            const int c = tg[s >> 1];
-            int head = 1, nx = 0;
-            for (int q = 1; q < s; q += 2) if (tg[q >> 1] == c) { head = 0; break; }
-            for (int q = s + 2; q < S; q += 2) if (tg[q >> 1] == c) { nx = q + 1; break; }
-            chain[(long)b * Sp + s] = nx | (head << 16);
-        }
+        ctc_link_chains(lane, S, tg, chain + (long)b * Sp);
     } else if (Tb > 0) {
         double a[NS];
         if (wv == 0) {
@@ -668,7 +508,7 @@ __global__ __launch_bounds__(192) void ctc_alphabeta_f64_kernel(int T, const int
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        // as ctc_alphabeta_block: anything that still carries the "log 0" scale is an infeasible alignment
+        // as ctc_alphabeta_kernel: anything that still carries the "log 0" scale is an infeasible alignment
         double ll = -INFINITY;
         if (Tb > 0) {
             const double m = fmax(fin[0], fin[1]);
@@ -687,47 +527,8 @@ __global__ __launch_bounds__(256) void ctc_labels_f64_kernel(long rows, int B, i
                                                               float scale, const float* __restrict__ utt_weight,
                                                               float* __restrict__ dlogits, float* __restrict__ loss_sum) {
     extern __shared__ __attribute__((aligned(16))) float sh[];   // per wave: gam[Sp]
-    ctc_labels_block<true, double>(sh, blockIdx.x, rows, B, T, V, ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_in, chain, nll,
-                                   scale, utt_weight, dlogits, loss_sum, 0, T);
-}
-
-// overlapped form, launch 3: blocks 0 .. nlab-1 = the label fix-up of four frames each (all frames), the rest = dense rows
-template <int NV4>
-__global__ __launch_bounds__(256) void ctc_labels_dense_kernel(long nlab, const float* logits, int B, int T, int V, long ldv,
-                                                               const int* __restrict__ hlens, const int* __restrict__ targets, int Lmax,
-                                                               const int* __restrict__ tlens, int Sp, const float* __restrict__ lp,
-                                                               const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                               const float* __restrict__ ll_in, const int* __restrict__ chain,
-                                                               const float* __restrict__ nll, float scale, const float* __restrict__ utt_weight,
-                                                               const float2* __restrict__ rowstat, float* dlogits, int t0, int Tc) {
-    extern __shared__ __attribute__((aligned(16))) float sh[];   // per wave: gam[Sp] (label blocks)
-    __shared__ unsigned maskw[4][NV4 * 8];
-    if ((long)blockIdx.x < nlab) {
-        ctc_labels_block<false>(sh, blockIdx.x, (long)B * T, B, T, V, ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_in, chain, nll,
-                                scale, utt_weight, dlogits, nullptr, 0, T);
-        return;
-    }
-    const int wv = threadIdx.x >> 6;
-    ctc_dense_row<NV4>(logits, ldv, (long)B * Tc, T, V, hlens, targets, Lmax, tlens, scale, utt_weight, rowstat, dlogits, t0, Tc,
-                       ((long)blockIdx.x - nlab) * 4 + wv, maskw[wv]);
-}
-// overlapped form, last launch: one block per utterance zeroes the rows of an infeasible utterance (zero_infinity; the live frames
-// only - padded frames are zero already); block 0 also sums the loss
-__global__ __launch_bounds__(256) void ctc_final_kernel(int B, int T, int V, long ldv, const int* __restrict__ hlens, const float* __restrict__ ll_in,
-                                                         const float* __restrict__ nll, const float* __restrict__ utt_weight,
-                                                         float* __restrict__ dlogits, float* __restrict__ loss_sum) {
-    const int b = blockIdx.x;
-    if (loss_sum && b == 0 && threadIdx.x < 64) {
-        float s = 0.f;
-        for (int i = threadIdx.x; i < B; i += 64) s += utt_weight ? nll[i] * utt_weight[i] : nll[i];
-        s = wave_sum(s);
-        if (threadIdx.x == 0) loss_sum[0] = s;
-    }
-    if (ll_in[b] != NEG_INF) return;
-    const int Tb = min(hlens[b], T);
-    float* g = dlogits + (long)b * T * ldv;
-    for (int t = 0; t < Tb; ++t)
-        for (int i = threadIdx.x; i < V; i += 256) g[(long)t * ldv + i] = 0.f;
+    ctc_labels_block<double>(sh, blockIdx.x, rows, B, T, V, ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll_in, chain, nll,
+                             scale, utt_weight, dlogits, loss_sum, 0, T);
 }
 
 __global__ void ctc_sum_kernel(const float* __restrict__ nll, const float* __restrict__ utt_weight, int B, float* __restrict__ out) {
@@ -765,15 +566,12 @@ static CtcPipe* ctc_pipe() {
 }
 
 // OE_CTC_PIPE: 0 = rows, alpha/beta, labels one after the other (default); 1 / 2 = chunk pipeline on two streams where the batch
-// is large enough / always; 3 / 4 = the overlapped form (mixed launches, ctc_dense_row) for large batches / always;
-// OE_CTC_CHUNKS: time chunks of the chunk pipeline.  Both alternatives are bit-for-bit / tolerance-equal (tests run them) and both
-// measured SLOWER than the default on MI355X (profiles/r03_experiments.md) - overlapped form at B = 64 x 16 s: statistics pass 86 us
-// (a read-only sweep of the logits runs at 3.8 TB/s where the read + write `rows` pass moves 6.0), recursion beside dense rows 100 us
-// (59 alone), fix-up beside dense rows 101 us: 294 us against 208; the streaming blocks take the memory system's latency up and the
-// latency-bound blocks (the recursion's prefetch, the fix-up's dependent loads) stretch by what the overlap was to hide.
-// Measured on MI355X (tools/ctc_graph_bench.py, profiles/r03_experiments.md): every cross-stream edge of the pipelined form
-// costs more than the chain time it hides - from a HIP graph 216 us sequential against 335 / 352 / 384 / 436 us with 2 / 3 /
-// 4 / 6 chunks at the north-star shape (eager launches: 209 against 310 with 4) - so it is not the default.
+// is large enough / always; OE_CTC_CHUNKS: its time chunks.  The pipeline is bit-for-bit equal (tests run it) and measured SLOWER
+// than the default on MI355X (tools/ctc_graph_bench.py, profiles/r03_experiments.md): every cross-stream edge costs more than the
+// chain time it hides - from a HIP graph 216 us sequential against 335 / 352 / 384 / 436 us with 2 / 3 / 4 / 6 chunks at the
+// north-star shape (eager launches: 209 against 310 with 4) - so it is not the default.
+// An overlapped form (row statistics first, then mixed launches of recursion / fix-up blocks beside dense-gradient blocks; modes
+// 3 / 4) was also measured slower, 294 us against 208, and removed: profiles/r03_experiments.md.
 static int ctc_pipe_mode = getenv("OE_CTC_PIPE") ? atoi(getenv("OE_CTC_PIPE")) : 0;
 static int ctc_pipe_chunks = getenv("OE_CTC_CHUNKS") ? atoi(getenv("OE_CTC_CHUNKS")) : 4;
 extern "C" int oe_ctc_config(int pipe_mode, int chunks) {
@@ -800,30 +598,39 @@ static int ctc_f32_max_t = getenv("OE_CTC_F32_MAX_T") ? atoi(getenv("OE_CTC_F32_
 
 extern "C" size_t oe_ctc_workspace_floats(int B, int T, int Lmax) {
     size_t Sp = 2 * (size_t)Lmax + 1;
-    size_t n = (size_t)B + 3 * (size_t)B * T * Sp + (size_t)B * Sp + 16 + 2 * (size_t)B * T + 2;  // .. + row statistics of the overlapped form
+    size_t n = (size_t)B + 3 * (size_t)B * T * Sp + (size_t)B * Sp + 16;          // ll, lp, alpha, beta, chain, 16 spare floats
     if (T > ctc_f32_max_t) n += 2 * (size_t)B * T * Sp + 2 * (size_t)B + 2;      // alpha, beta, ll in float64, 8-byte aligned
     return n;
 }
 
-static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets,
-                         int Lmax, const int* tlens, float grad_scale, const float* utt_weight, float* nll,
-                         float* loss_sum, float* dlogits, float* workspace, const float* row_stats, int stats_groups, void* stream);
+// k1 over frames t0 .. t0 + tc - 1 of every utterance, for the loss (both state widths) and the aligner: the row variant the
+// pointers and V allow, with the dense gradient when dlogits is given.
+static void ctc_launch_rows(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets, int Lmax,
+                            const int* tlens, int Sp, float scale, const float* utt_weight, float* lp, float* dlogits, int t0, int tc,
+                            hipStream_t st) {
+    const long rows = (long)B * tc;
+    // register-resident rows need 16-byte aligned rows that are padded to whole float4s
+    const bool vec = (((uintptr_t)logits & 15) == 0) && (!dlogits || ((uintptr_t)dlogits & 15) == 0) && (ldv % 4 == 0) &&
+                     (ldv >= (((long)V + 3) & ~3L)) && V <= 256 * 32;
+    const int nv4 = !vec ? 0 : V <= 256 * 4 ? 4 : V <= 256 * 8 ? 8 : V <= 256 * 16 ? 16 : 32;
+#define ROWS(NV4, WR)                                                                                                            \
+    hipLaunchKernelGGL((ctc_rows_kernel<NV4, WR>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, hlens, targets, \
+                       Lmax, tlens, Sp, scale, utt_weight, lp, dlogits, t0, tc)
+#define ROWS_W(NV4) do { if (dlogits) ROWS(NV4, true); else ROWS(NV4, false); } while (0)
+    switch (nv4) {
+        case 4: ROWS_W(4); break;
+        case 8: ROWS_W(8); break;
+        case 16: ROWS_W(16); break;
+        case 32: ROWS_W(32); break;
+        default: ROWS_W(0); break;
+    }
+#undef ROWS_W
+#undef ROWS
+}
+
 extern "C" int oe_ctc_loss_fused(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets,
                                  int Lmax, const int* tlens, float grad_scale, const float* utt_weight, float* nll,
                                  float* loss_sum, float* dlogits, float* workspace, void* stream) {
-    return ctc_loss_impl(logits, ldv, B, T, V, hlens, targets, Lmax, tlens, grad_scale, utt_weight, nll, loss_sum, dlogits, workspace, nullptr, 0, stream);
-}
-extern "C" int oe_ctc_loss_fused_stats(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets,
-                                       int Lmax, const int* tlens, float grad_scale, const float* utt_weight, float* nll,
-                                       float* loss_sum, float* dlogits, float* workspace, const float* row_stats, int stats_groups, void* stream) {
-    OE_REQUIRE(!row_stats || (stats_groups == (V + 31) / 32 && (((uintptr_t)row_stats) & 7) == 0),
-               "oe_ctc_loss_fused_stats: row_stats must hold ceil(V / 32) = %d (max, sum) pairs per row, 8-byte aligned (got %d groups)", (V + 31) / 32, stats_groups);
-    return ctc_loss_impl(logits, ldv, B, T, V, hlens, targets, Lmax, tlens, grad_scale, utt_weight, nll, loss_sum, dlogits, workspace, row_stats, stats_groups, stream);
-}
-
-static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* targets,
-                         int Lmax, const int* tlens, float grad_scale, const float* utt_weight, float* nll,
-                         float* loss_sum, float* dlogits, float* workspace, const float* row_stats, int stats_groups, void* stream) {
     OE_REQUIRE(logits && hlens && tlens && nll && workspace, "oe_ctc_loss_fused: null pointer");
     OE_REQUIRE(targets || Lmax == 0, "oe_ctc_loss_fused: null targets");
     OE_REQUIRE(B > 0 && T > 0 && V > 1 && Lmax >= 0 && ldv >= V, "oe_ctc_loss_fused: bad shape B=%d T=%d V=%d Lmax=%d ldv=%ld",
@@ -838,11 +645,9 @@ static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, con
     int* chain = reinterpret_cast<int*>(beta + (size_t)B * T * Sp);
     float* dump = reinterpret_cast<float*>(chain + (size_t)B * Sp);      // the 16 spare floats at the end
     const long rows = (long)B * T;
-    // register-resident rows need 16-byte aligned rows that are padded to whole float4s
-    const bool vec = (((uintptr_t)logits & 15) == 0) && (!dlogits || ((uintptr_t)dlogits & 15) == 0) && (ldv % 4 == 0) &&
-                     (ldv >= (((long)V + 3) & ~3L)) && V <= 256 * 32;
-    const int nv4 = !vec ? 0 : V <= 256 * 4 ? 4 : V <= 256 * 8 ? 8 : V <= 256 * 16 ? 16 : 32;
-    float2* rowstat = reinterpret_cast<float2*>((reinterpret_cast<uintptr_t>(dump + 16) + 7) & ~(uintptr_t)7);
+    auto launch_rows = [&](int t0, int tc) {
+        ctc_launch_rows(logits, ldv, B, T, V, hlens, targets, Lmax, tlens, Sp, grad_scale, utt_weight, lp, dlogits, t0, tc, st);
+    };
     // ---- float64-state path (see ctc_f32_max_t): rows, alpha/beta, labels one after the other whatever the launch form asked for.
     // Workspace: ll (unused), lp, then chain, and behind it ll / alpha / beta / two dump words as doubles.
     if (T > ctc_f32_max_t) {
@@ -851,12 +656,7 @@ static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, con
         double* alpha64 = ll64 + B;
         double* beta64 = alpha64 + (size_t)B * T * Sp;
         double* dump64 = beta64 + (size_t)B * T * Sp;
-#define ROWS64(NV4) do { if (dlogits) hipLaunchKernelGGL((ctc_rows_kernel<NV4, true>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, \
-                                                         hlens, targets, Lmax, tlens, Sp, grad_scale, utt_weight, lp, dlogits, 0, T, nullptr);               \
-                         else hipLaunchKernelGGL((ctc_rows_kernel<NV4, false>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V,           \
-                                                 hlens, targets, Lmax, tlens, Sp, grad_scale, utt_weight, lp, dlogits, 0, T, nullptr); } while (0)
-        if (nv4 == 4) ROWS64(4); else if (nv4 == 8) ROWS64(8); else if (nv4 == 16) ROWS64(16); else if (nv4 == 32) ROWS64(32); else ROWS64(0);
-#undef ROWS64
+        launch_rows(0, T);
         OE_LAUNCH_CHECK("ctc_rows");
 #define AB64(NS, CH) hipLaunchKernelGGL((ctc_alphabeta_f64_kernel<NS, CH>), dim3(B), dim3(192), 0, st, T, hlens, targets, Lmax, tlens, \
                                         Sp, lp, alpha64, beta64, ll64, nll, chain64, dump64)
@@ -873,50 +673,6 @@ static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, con
         }
         return 0;
     }
-    // ---- overlapped form (see ctc_dense_row): statistics, chains + first half of the dense rows, fix-up + second half, final
-    const int pipe_mode0 = ctc_pipe_mode;
-    if (dlogits && nv4 > 0 && (pipe_mode0 == 4 || (pipe_mode0 == 3 && (double)rows * V >= 2.0e7))) {
-        if (row_stats) {
-            hipLaunchKernelGGL(ctc_lp_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, hlens, targets, Lmax, tlens, Sp,
-                               reinterpret_cast<const float2*>(row_stats), stats_groups, lp, rowstat);
-        } else {
-#define STATS(NV4) hipLaunchKernelGGL((ctc_rows_kernel<NV4, false>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, hlens, targets, \
-                                      Lmax, tlens, Sp, grad_scale, utt_weight, lp, nullptr, 0, T, rowstat)
-            if (nv4 == 4) STATS(4); else if (nv4 == 8) STATS(8); else if (nv4 == 16) STATS(16); else STATS(32);
-#undef STATS
-        }
-        OE_LAUNCH_CHECK("ctc_stats");
-        const int T1 = T / 2;
-        const long nd1 = oe_cdiv((long)B * T1, 4), nd2 = oe_cdiv((long)B * (T - T1), 4), nlab = oe_cdiv(rows, 4);
-#define K2(NV4, NS, CH) hipLaunchKernelGGL((ctc_chain_dense_kernel<NV4, NS, CH>), dim3(B + nd1), dim3(256), 0, st, B, logits, ldv, T, V, hlens, targets, Lmax, \
-                                           tlens, Sp, lp, alpha, beta, ll, nll, chain, dump, grad_scale, utt_weight, rowstat, dlogits, 0, T1)
-#define K2S(NV4) do { if (Sp <= 64) K2(NV4, 1, 32); else if (Sp <= 128) K2(NV4, 2, 16); else if (Sp <= 256) K2(NV4, 4, 8); else K2(NV4, 8, 4); } while (0)
-        if (nv4 == 4) K2S(4); else if (nv4 == 8) K2S(8); else if (nv4 == 16) K2S(16); else K2S(32);
-#undef K2S
-#undef K2
-        OE_LAUNCH_CHECK("ctc_chain_dense");
-#define K3(NV4) hipLaunchKernelGGL((ctc_labels_dense_kernel<NV4>), dim3(nlab + nd2), dim3(256), (size_t)4 * Sp * sizeof(float), st, nlab, logits, B, T, V, ldv, \
-                                   hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll, chain, nll, grad_scale, utt_weight, rowstat, dlogits, T1, T - T1)
-        if (nv4 == 4) K3(4); else if (nv4 == 8) K3(8); else if (nv4 == 16) K3(16); else K3(32);
-#undef K3
-        OE_LAUNCH_CHECK("ctc_labels_dense");
-        hipLaunchKernelGGL(ctc_final_kernel, dim3(B), dim3(256), 0, st, B, T, V, ldv, hlens, ll, nll, utt_weight, dlogits, loss_sum);
-        OE_LAUNCH_CHECK("ctc_final");
-        return 0;
-    }
-#define ROWS(NV4, WR, T0, TC)                                                                                                  \
-    hipLaunchKernelGGL((ctc_rows_kernel<NV4, WR>), dim3(oe_cdiv((long)B * (TC), 4)), dim3(256), 0, st, logits, ldv, (long)B * (TC), T, V, \
-                       hlens, targets, Lmax, tlens, Sp, grad_scale, utt_weight, lp, dlogits, T0, TC, nullptr)
-#define ROWS_W(NV4, T0, TC) do { if (dlogits) ROWS(NV4, true, T0, TC); else ROWS(NV4, false, T0, TC); } while (0)
-    auto launch_rows = [&](int t0, int tc) {
-        switch (nv4) {
-            case 4: ROWS_W(4, t0, tc); break;
-            case 8: ROWS_W(8, t0, tc); break;
-            case 16: ROWS_W(16, t0, tc); break;
-            case 32: ROWS_W(32, t0, tc); break;
-            default: ROWS_W(0, t0, tc); break;
-        }
-    };
     auto launch_labels = [&](int t0, int tc, float* lsum) {
         hipLaunchKernelGGL(ctc_labels_kernel, dim3(oe_cdiv((long)B * tc, 4)), dim3(256), (size_t)4 * Sp * sizeof(float), st, (long)B * tc, B, T, V,
                            ldv, hlens, targets, Lmax, tlens, Sp, lp, alpha, beta, ll, chain, nll, grad_scale, utt_weight, dlogits, lsum, t0, tc);
@@ -968,8 +724,6 @@ static int ctc_loss_impl(const float* logits, long ldv, int B, int T, int V, con
         return 0;
     }
     launch_rows(0, T);
-#undef ROWS_W
-#undef ROWS
     OE_LAUNCH_CHECK("ctc_rows");
 #define AB(NS, CH) hipLaunchKernelGGL((ctc_alphabeta_kernel<NS, CH>), dim3(B), dim3(192), 0, st, T, hlens, targets, Lmax, tlens, \
                                       Sp, lp, alpha, beta, ll, nll, chain, dump)
@@ -1266,19 +1020,7 @@ extern "C" int oe_ctc_align(const float* logits, long ldv, int B, int T, int V, 
     hipStream_t st = (hipStream_t)stream;
     float* lp = reinterpret_cast<float*>(workspace);
     void* bp = reinterpret_cast<char*>(workspace) + (((size_t)B * T * Sp * sizeof(float) + 15) & ~(size_t)15);
-    const long rows = (long)B * T;
-    const bool vec = (((uintptr_t)logits & 15) == 0) && (ldv % 4 == 0) && (ldv >= (((long)V + 3) & ~3L)) && V <= 256 * 32;
-    const int nv4 = !vec ? 0 : V <= 256 * 4 ? 4 : V <= 256 * 8 ? 8 : V <= 256 * 16 ? 16 : 32;
-#define ROWS(NV4) hipLaunchKernelGGL((ctc_rows_kernel<NV4, false>), dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, logits, ldv, rows, T, V, hlens, targets, \
-                                     Lmax, tlens, Sp, 0.f, nullptr, lp, nullptr, 0, T, nullptr)
-    switch (nv4) {
-        case 4: ROWS(4); break;
-        case 8: ROWS(8); break;
-        case 16: ROWS(16); break;
-        case 32: ROWS(32); break;
-        default: ROWS(0); break;
-    }
-#undef ROWS
+    ctc_launch_rows(logits, ldv, B, T, V, hlens, targets, Lmax, tlens, Sp, 0.f, nullptr, lp, nullptr, 0, T, st);
     OE_LAUNCH_CHECK("ctc_align_rows");
     const bool in_lds = ctc_align_in_lds(T, Sp);
     const size_t shm = in_lds ? (size_t)T * 64 * ctc_align_word(Sp) : 0;

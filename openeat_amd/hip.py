@@ -256,7 +256,6 @@ _SIGNATURES = {
     "oe_ctc_workspace_floats": (SZ, [I, I, I]),
     "oe_ctc_config": (I, [I, I]),
     "oe_ctc_loss_fused": (I, [P, L, I, I, I, P, P, I, P, F, P, P, P, P, P, P]),
-    "oe_ctc_loss_fused_stats": (I, [P, L, I, I, I, P, P, I, P, F, P, P, P, P, P, P, I, P]),
     "oe_ctc_greedy": (I, [P, L, I, I, I, P, I, P, P, P, P]),
     "oe_ctc_align_workspace_bytes": (SZ, [I, I, I]),
     "oe_ctc_align": (I, [P, L, I, I, I, P, P, I, P, P, P, P, P, P, P, P]),

@@ -20,7 +20,7 @@ V = 3246
 Vp = (V + 3) // 4 * 4
 PEAK = 8.0e12
 ALIGN = "--align" in sys.argv[1:]
-FORMS = {0: "three launches", 3: "overlapped where profitable", 4: "overlapped", 1: "chunk pipeline", 2: "chunk pipeline (forced)"}
+FORMS = {0: "three launches", 1: "chunk pipeline", 2: "chunk pipeline (forced)"}
 for name, B, T, L in [("config 2 (B=32 x 10 s)", 32, 248, 30), ("north star (B=64 x 16 s)", 64, 398, 48)]:
     torch.manual_seed(0)
     src = torch.randn(B, T, Vp, device="cuda")
@@ -61,7 +61,7 @@ for name, B, T, L in [("config 2 (B=32 x 10 s)", 32, 248, 30), ("north star (B=6
               f"{l:8.1f} us (runs {', '.join('%.1f' % x for x in t_loss)}): ratio {a / l:.2f}; mean score {float(score.mean()):.3f}, "
               f"-loss/B {-float(tot) / B:.3f}")
         continue
-    for form in (int(x) for x in os.environ.get("CTC_BENCH_FORMS", "0,4").split(",")):
+    for form in (int(x) for x in os.environ.get("CTC_BENCH_FORMS", "0").split(",")):
         hip.lib().oe_ctc_config(form, 4)
         n = 20
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
