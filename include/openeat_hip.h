@@ -463,6 +463,73 @@ typedef struct oe_ctc_segment_args {
 size_t oe_ctc_segment_workspace_bytes(int B, int T, int V, int Lmax);
 int oe_ctc_segment(const oe_ctc_segment_args* args, void* stream);
 
+/* Keyword search over CTC posteriors on device (keyword spotting / spoken-term detection): for every recording b and every
+ * keyword k of a list, WHERE the keyword occurs and how confidently - every occurrence, not one placement.  The reference has
+ * none; these are the semantics every layer refers to.  With Tb = hlens[b], lp[t,v] the natural-log posterior, keyword k's
+ * labels y = y_1..y_L (L = klens[k], 1 <= L <= 32) and ext[s] as in oe_ctc_align (odd s: y[s >> 1], even s: blank 0), only
+ * the states 1 .. 2L-1 exist: a keyword starts in its first label and ends in its last, no blank state before or after it -
+ * at most 63 states, one per lane of a wave.  Each state carries a value v (float32) and the frame st at which its path
+ * entered state 1:
+ *   v[t,s] = lp[t,ext[s]] + the best of   stay  v[t-1,s]
+ *                                        step  v[t-1,s-1]   (s >= 2)
+ *                                        skip  v[t-1,s-2]   (odd s >= 3 with ext[s] != ext[s-2])
+ *                                        fresh 0, with st = t   (s == 1 only)
+ *   tried in that order; a candidate replaces the best only if strictly greater (oe_ctc_align's tie rule) and st travels with
+ *   the winner.  At t = 0 only fresh exists.  A state with no predecessor is unreachable, and an unreachable state is never a
+ *   candidate below, whatever finite stand-in for -inf the kernel uses (lp is expected finite).
+ *   Candidate: at every frame t at which state 2L-1 is reachable, the span [st, t] with n = t - st + 1 frames and the score
+ *   sc = v[t,2L-1]: the log-probability of the best path that spells the keyword and ends at t, its start free.
+ *   Comparisons between candidates are exact, in float64 and without a division: a is better than b iff
+ *   (double)a.sc * b.n > (double)b.sc * a.n (the mean log-probability per frame); a candidate passes the threshold iff
+ *   (double)sc >= (double)thr[k] * n.
+ *   Hits: per (b,k), t ascending, one pending hit.  A passing candidate whose st <= the pending hit's end overlaps it and
+ *   replaces it iff it is better; one that does not overlap has the pending hit emitted and becomes the pending one; after
+ *   the last frame the pending hit is emitted.  The emitted hits are in time order and disjoint.
+ *   out (device memory):
+ *        n_hits (B, K) int32 = the number of hits emitted; may exceed max_hits;
+ *        hit_start / hit_end (B, K, max_hits) int32 = the spans of the first max_hits hits, -1 in unused slots;
+ *        hit_score (B, K, max_hits) float32 = their sc, 0 in unused slots;
+ *        best_start / best_end (B, K) int32, best_score (B, K) float32, each or NULL = the best candidate over all frames
+ *        whatever the threshold, the earliest kept on ties; -1 / -1 / -inf if there never was a candidate.
+ *   klens[k] == 0 or Tb == 0: no hits, no best.  Tb is hlens[b] held to [0, T], L is klens[k] held to [0, Lmax].
+ *   Labels are expected in [1, V); one outside [0, V) is read as the nearest valid column, never out of bounds, as in
+ *   oe_ctc_segment; ext[s] != ext[s-2] compares the labels as given (their indices in cols).
+ *   A property, not a defect: a fresh start costs 0 and every scored frame costs at most 0, so a span is as tight as
+ *   optimality allows: it starts with the last frame of the first label's run and a candidate ends where the last label is
+ *   entered or held.  A keyword of one label has one-frame candidates.
+ *   normalized = 0: logits are raw and lp = logits - c_t with c_t the row's log-sum-exp;  normalized = 1: the rows are used as
+ *   given (callers that hold log-probabilities; values on a coarse binary grid make every float32 sum exact).
+ *   The keyword list is one struct, host memory read during the call only, its four pointers device pointers (built by
+ *   openeat_amd/utils/keyword.py): cols (U) the distinct tokens of all keywords, ascending; kw_col (K, Lmax) the index into
+ *   cols of each label (held to [0, U)); klens (K); thr (K) the mean natural-log-probability per frame a hit must reach.
+ *   Limits: 1 <= B, 1 <= T <= 2^20, 1 <= K <= 65535, 1 <= Lmax <= 32, 1 <= U < V, ldv >= V, max_hits >= 1.  Anything else,
+ *   and any NULL required pointer (logits, hlens, kws and its four tables, n_hits, hit_start, hit_end, hit_score, workspace),
+ *   is reported through oe_last_error before any launch, with the outputs untouched.
+ *   workspace: oe_ctc_kws_workspace_bytes(B,T,U) = B*T*(U+1) floats, 16-byte aligned (0 for shapes outside the limits): per
+ *   frame the blank and the U keyword columns as lp.  Keywords are independent, so a caller short of memory runs them in groups.
+ * Two launches (one wave per frame: every logits row is read once, its log-sum-exp taken and its U+1 columns kept; one wave
+ * per (b,k): recursion and scan, the start frame carried, not traced - no (B,K,T) table, no back-pointers).  No workgroup
+ * waits for another, no atomics; no allocation, no host read, no host-side state: capturable. */
+typedef struct oe_keyword_set {
+    const int* cols;      /* (U) the distinct tokens of all keywords, ascending */
+    int U;
+    const int* kw_col;    /* (K,Lmax) index into cols of each label */
+    const int* klens;     /* (K) */
+    const float* thr;     /* (K) mean natural-log-probability per frame a hit must reach */
+    int K, Lmax;
+} oe_keyword_set;
+typedef struct oe_ctc_kws_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_keyword_set* kws;
+    int normalized, max_hits;
+    int* n_hits; int* hit_start; int* hit_end; float* hit_score;
+    int* best_start; int* best_end; float* best_score;
+    void* workspace;
+} oe_ctc_kws_args;
+size_t oe_ctc_kws_workspace_bytes(int B, int T, int U);
+int oe_ctc_kws(const oe_ctc_kws_args* args, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

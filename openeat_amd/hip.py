@@ -215,6 +215,20 @@ class CtcSegmentArgs(C.Structure):
                 ("workspace", c_fp)]
 
 
+class KeywordSet(C.Structure):
+    """oe_keyword_set (include/openeat_hip.h); filled by keyword_set."""
+    _fields_ = [("cols", c_fp), ("U", C.c_int), ("kw_col", c_fp), ("klens", c_fp), ("thr", c_fp), ("K", C.c_int), ("Lmax", C.c_int)]
+
+
+class CtcKwsArgs(C.Structure):
+    """oe_ctc_kws_args (include/openeat_hip.h); filled by ops.ctc_keyword_search.  A struct assigned through C.pointer to kws
+    stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("kws", C.POINTER(KeywordSet)), ("normalized", C.c_int), ("max_hits", C.c_int),
+                ("n_hits", c_fp), ("hit_start", c_fp), ("hit_end", c_fp), ("hit_score", c_fp),
+                ("best_start", c_fp), ("best_end", c_fp), ("best_score", c_fp), ("workspace", c_fp)]
+
+
 I, L, F, D, P, U64, SZ =C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
@@ -261,6 +275,8 @@ _SIGNATURES = {
     "oe_ctc_align": (I, [P, L, I, I, I, P, P, I, P, P, P, P, P, P, P, P]),
     "oe_ctc_segment_workspace_bytes": (SZ, [I, I, I, I]),
     "oe_ctc_segment": (I, [C.POINTER(CtcSegmentArgs), P]),
+    "oe_ctc_kws_workspace_bytes": (SZ, [I, I, I]),
+    "oe_ctc_kws": (I, [C.POINTER(CtcKwsArgs), P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),
@@ -587,6 +603,16 @@ def context_graph(graph, device) -> ContextGraph:
                      graph.n_states, float(graph.context_score))
     g.owner = graph                                                # the pointers live as long as the struct
     return g
+
+
+def keyword_set(keywords, device) -> KeywordSet:
+    """The oe_keyword_set of `keywords`, an openeat_amd.utils.keyword.KeywordList, with its tables on `device` (the list keeps
+    them, the struct keeps the list)."""
+    cols, kw_col, klens, thr = keywords.device_tables(device)
+    q = KeywordSet(cols.data_ptr(), int(cols.shape[0]), kw_col.data_ptr(), klens.data_ptr(), thr.data_ptr(), int(kw_col.shape[0]),
+                   int(kw_col.shape[1]))
+    q.owner = keywords                                             # the pointers live as long as the struct
+    return q
 
 
 def prefix_beam_args(top_logp, top_idx, lens, beam, max_len, ws, prefixes, plen, score, ctc=None, lms=None, bias=None, *, lm=None,

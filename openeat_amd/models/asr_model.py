@@ -450,6 +450,30 @@ class ASRModel(torch.nn.Module):
         return out
 
     @torch.no_grad()
+    def keyword_search(self, features: torch.Tensor, features_length: torch.Tensor, keywords, window: Optional[int] = None,
+                       margin: int = 16, max_hits: int = 8, with_times: bool = False, frame_shift_ms: float = 10):
+        """Keyword search (spoken-term detection; the reference has none; semantics in include/openeat_hip.h, oe_ctc_kws): where
+        each keyword of `keywords`, an openeat_amd.utils.keyword.KeywordList, occurs in each recording - every occurrence whose
+        mean posterior per frame reaches the keyword's threshold, not the 1-best's.  Logits by ctc_logits_windowed (window
+        None: one plain pass), recursion and hit scan on the device, one D2H copy of the results.  Returns (hits, truncated):
+        hits[b] the recording's hits in time order, each {"keyword": index, "tokens", "start_frame", "end_frame" (inclusive
+        encoder frames), "score" (log-probability of the hit's path), "confidence" = exp(score / frames), and with_times
+        "start_s" / "end_s"}; truncated[b][k]: more than max_hits hits were found and only the first max_hits are listed."""
+        from openeat_amd.utils.keyword import KeywordList, hit_records
+        if not isinstance(keywords, KeywordList):
+            raise ValueError(f"keywords must be an openeat_amd.utils.keyword.KeywordList (got {type(keywords).__name__})")
+        assert features.shape[0] == features_length.shape[0]
+        logits, lens = self.ctc_logits_windowed(features, features_length, window, margin)
+        n_hits, start, end, score = ops.ctc_keyword_search(logits, lens, keywords, max_hits)[:4]
+        B, K = n_hits.shape
+        packed = torch.cat([n_hits.double().flatten(), start.double().flatten(), end.double().flatten(), score.double().flatten()]).cpu()
+        n, s, e, sc = packed[: B * K], *packed[B * K:].split(B * K * max_hits)
+        shape = (B, K, max_hits)
+        rate = self.encoder.embed.subsampling_rate
+        times = (lambda a, b: frame_times(a, b, rate, frame_shift_ms)) if with_times else None
+        return hit_records(keywords, n.view(B, K).tolist(), s.view(shape).tolist(), e.view(shape).tolist(), sc.view(shape).tolist(), times)
+
+    @torch.no_grad()
     def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],
                           margin: int = 16):
         """The per-frame top-`beam_size` CTC log-probabilities of whole recordings, window by window: a generator over

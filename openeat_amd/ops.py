@@ -2397,6 +2397,55 @@ def ctc_segment(logits, ldv, B, T, V, hlens, ys, ylens, free_start=True, free_en
     return frames, path_logp, start[:, :Lmax], end[:, :Lmax], tok_logp[:, :Lmax], score
 
 
+def ctc_keyword_search(logits, hlens, keywords, max_hits=8, normalized=False, max_workspace_bytes=1 << 30):
+    """Keyword search over CTC posteriors (oe_ctc_kws; semantics in include/openeat_hip.h): logits (B, T, V) float32 (raw, or
+    log-probabilities with normalized=True), hlens (B), keywords an openeat_amd.utils.keyword.KeywordList -> device tensors
+    (n_hits (B, K) int32, hit_start, hit_end (B, K, max_hits) int32, hit_score (B, K, max_hits) float32, best_start, best_end
+    (B, K) int32, best_score (B, K) float32).  The workspace is B * T * (U + 1) floats for the U distinct tokens of the list;
+    where that exceeds max_workspace_bytes the keywords - they are independent - run in consecutive groups of at most as many
+    distinct tokens as fit, one workspace reused, and the results are concatenated: exactly those of one call."""
+    from openeat_amd.utils.keyword import KeywordList
+    if not isinstance(keywords, KeywordList):
+        raise TypeError(f"ctc_keyword_search: keywords must be an openeat_amd.utils.keyword.KeywordList (got {type(keywords).__name__})")
+    logits = _chk(logits, "ctc_keyword_search")
+    if logits.dim() != 3:
+        raise ValueError(f"ctc_keyword_search: logits must be (B, T, V), got {tuple(logits.shape)}")
+    B, T, V = logits.shape
+    dev = logits.device
+    K, max_hits = len(keywords), int(max_hits)
+    if B < 1 or not 1 <= T <= 1 << 20 or max_hits < 1 or len(keywords.cols) >= V:
+        raise ValueError(f"ctc_keyword_search: B={B} T={T} max_hits={max_hits} U={len(keywords.cols)} V={V} outside 1 <= B, "
+                         "1 <= T <= 2^20, 1 <= max_hits, U < V")
+    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
+    max_cols = max(int(max_workspace_bytes) // (4 * B * T) - 1, 1)
+    bounds = keywords.group_bounds(max_cols) if len(keywords.cols) > max_cols else [0, K]
+    n_hits = torch.empty(B, K, dtype=torch.int32, device=dev)
+    hit_start = torch.empty(B, K, max_hits, dtype=torch.int32, device=dev)
+    hit_end = torch.empty(B, K, max_hits, dtype=torch.int32, device=dev)
+    hit_score = torch.empty(B, K, max_hits, dtype=torch.float32, device=dev)
+    best_start = torch.empty(B, K, dtype=torch.int32, device=dev)
+    best_end = torch.empty(B, K, dtype=torch.int32, device=dev)
+    best_score = torch.empty(B, K, dtype=torch.float32, device=dev)
+    outs = (n_hits, hit_start, hit_end, hit_score, best_start, best_end, best_score)
+    groups = [keywords] if len(bounds) == 2 else [keywords.subset(lo, hi) for lo, hi in zip(bounds, bounds[1:])]
+    ws = torch.empty(max(hip.lib().oe_ctc_kws_workspace_bytes(B, T, len(g.cols)) for g in groups), dtype=torch.uint8, device=dev)
+    for g, lo, hi in zip(groups, bounds, bounds[1:]):
+        # one group: its own outputs (B, hi - lo, ..) - a slice of the full ones is not dense unless B == 1 or the group is all
+        part = outs if len(groups) == 1 else tuple(o.new_empty((B, hi - lo) + tuple(o.shape[2:])) for o in outs)
+        a = hip.CtcKwsArgs()
+        a.logits, a.ldv, a.B, a.T, a.V = logits.data_ptr(), V, B, T, V
+        a.hlens, a.kws = hl32.data_ptr(), hip.C.pointer(hip.keyword_set(g, dev))
+        a.normalized, a.max_hits = int(bool(normalized)), max_hits
+        a.n_hits, a.hit_start, a.hit_end, a.hit_score = (t.data_ptr() for t in part[:4])
+        a.best_start, a.best_end, a.best_score = (t.data_ptr() for t in part[4:])
+        a.workspace = ws.data_ptr()
+        hip.check(hip.lib().oe_ctc_kws(hip.C.byref(a), hip.stream()), "oe_ctc_kws")
+        if part is not outs:
+            for o, q in zip(outs, part):
+                o[:, lo:hi] = q
+    return outs
+
+
 def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
     """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
     openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:
