@@ -530,6 +530,83 @@ typedef struct oe_ctc_kws_args {
 size_t oe_ctc_kws_workspace_bytes(int B, int T, int U);
 int oe_ctc_kws(const oe_ctc_kws_args* args, void* stream);
 
+/* Grammar-constrained CTC decoding on device: the best path of the CTC posteriors through an epsilon-free weighted token graph
+ * (a command list, a digit loop, words with several spellings, a transcript with alternatives), the CTC topology - blank,
+ * repeats - applied implicitly.  The reference has none (WeNet, which it derives from, ships it as TLG decoding); these are the
+ * semantics every layer refers to.
+ *   Graph: Q nodes, node 0 the start; A arcs, arc a with src[a], dst[a], a label label[a] in [1, V) (blank, 0, is never a
+ *   label) and a weight w[a] (float32, natural log, any finite value); final[q] float32, -inf = not final.  The graph may be
+ *   non-deterministic and may have self-loops, parallel arcs and unreachable nodes; there are no epsilon arcs.  Arcs are
+ *   stored sorted by dst, stable, with in_ptr (Q+1): the arcs into q are in_ptr[q] .. in_ptr[q+1]-1, and arc ids are positions
+ *   in this order.  As in oe_keyword_set, cols (U) holds the distinct labels ascending and col[a] the index of label[a] into
+ *   cols; "same label" means same col.  A label outside [0, V) is read as the nearest valid column, never out of bounds, as
+ *   in oe_ctc_segment and oe_ctc_kws (src, dst, col and in_ptr are likewise held to their ranges).
+ *   States, per utterance: a node state n[q] - the path is at q and the last frame was blank, or no frame was consumed yet -
+ *   and an arc state r[a] - the last frame emitted label[a] while traversing a.  Before frame 0, n[0] = 0 and every other
+ *   state is unreachable.  With Tb = hlens[b] held to [0, T] and lp as in oe_ctc_kws (normalized 0 or 1), for t = 0 .. Tb-1:
+ *     r_t[a] = lp[t,label[a]] + the best of   stay       r_{t-1}[a]
+ *                                             from node  n_{t-1}[src[a]] + w[a]
+ *                                             from arc   r_{t-1}[a'] + w[a], every a' with dst[a'] == src[a] and a label
+ *                                                        different from label[a]
+ *     n_t[q] = lp[t,0] + the best of          stay       n_{t-1}[q]
+ *                                             arrive     r_{t-1}[a'], every a' with dst[a'] == q
+ *   Ties (oe_ctc_align's rule, generalised): candidates are tried in the order stay, from node, then arcs by ascending id; a
+ *   candidate replaces the best only if strictly greater.  An unreachable state is never a candidate.
+ *   End: the winner is the best of n_{Tb-1}[q] + final[q] over q ascending, then r_{Tb-1}[a] + final[dst[a]] over a ascending,
+ *   a later candidate only if strictly greater.  Tb == 0 or no final state reachable: the utterance is infeasible.
+ *   On a linear chain with zero weights this is exactly oe_ctc_align's problem, ties included.
+ *   The recursion accumulates in float32 and adds w[a] to the maximum over the node and the arcs, not to each candidate: the
+ *   same winner wherever the sums are exact (values on a coarse binary grid); elsewhere the path is optimal up to float32
+ *   rounding and always a path the graph accepts.
+ *   out (device memory):
+ *        score (B) float32 = the winner's value, weights and final weight included; -inf if infeasible;
+ *        frames (B, T) int32 = the label emitted at each frame (label[a] as given), 0 for blank, -1 for t >= Tb or infeasible;
+ *        arcs (B, T) int32 = the arc id where the path is in an arc state, -1 elsewhere;
+ *        path_logp (B, T) float32 or NULL = lp[t, frames[t]], 0 for t >= Tb or infeasible;
+ *        n_trav (B) int32 = the number of arc traversals (0 if infeasible): a traversal starts at t iff arcs[t] >= 0 and
+ *        (t == 0 or arcs[t-1] != arcs[t]); may exceed max_trav;
+ *        trav_arc / trav_start / trav_end (B, max_trav) int32 = the first max_trav traversals, last frame inclusive, -1 in
+ *        unused slots;  trav_logp (B, max_trav) float32 or NULL = the float32 sum, in frame order, of lp over the traversal's
+ *        frames, 0 in unused slots.
+ *   The graph is one struct, host memory read during the call only, its pointers device pointers (built by
+ *   openeat_amd/utils/decoding_graph.py).
+ *   Limits: 1 <= B, 1 <= T <= 2^20, V > 1, ldv >= V, 1 <= U < V, max_trav >= 1, 1 <= Q <= OE_CTC_GRAPH_MAX_NODES,
+ *   1 <= A <= OE_CTC_GRAPH_MAX_ARCS: one workgroup holds 4 bytes per arc and 12 per node in the 160 KiB of LDS
+ *   (4 * 16384 + 12 * 8064 = 158.5 KiB, the rest its lists and reduction slots).  Anything else, and any NULL required pointer
+ *   (logits, hlens, graph and its eight tables, score, frames, arcs, n_trav, trav_arc, trav_start, trav_end, workspace), is
+ *   reported through oe_last_error before any launch, with the outputs untouched.
+ *   workspace: oe_ctc_graph_workspace_bytes(B,T,U,Q,A) bytes, 16-byte aligned (0 for shapes outside the limits):
+ *   B*T*(U+1) floats of lp as in oe_ctc_kws, then per frame a 4-byte back-pointer word per node and a byte per arc:
+ *   4 * B * T * (U + 1 + Q + ceil(A / 4)).  Utterances are independent, so a caller short of memory runs them in groups.
+ * Two launches (the row pass of oe_ctc_kws; one workgroup per utterance: recursion with the state values in LDS, back-trace,
+ * traversal list, score).  No workgroup waits for another, no float atomics; no allocation, no host read, no host-side state:
+ * capturable. */
+#define OE_CTC_GRAPH_MAX_NODES 8064
+#define OE_CTC_GRAPH_MAX_ARCS 16384
+typedef struct oe_decoding_graph {
+    int Q, A;
+    const int* in_ptr;    /* (Q+1) the arcs into q are in_ptr[q] .. in_ptr[q+1]-1 */
+    const int* src;       /* (A) */
+    const int* dst;       /* (A) ascending */
+    const int* label;     /* (A) */
+    const int* col;       /* (A) index of label[a] into cols */
+    const float* w;       /* (A) */
+    const float* final;   /* (Q) -inf: not final */
+    const int* cols;      /* (U) the distinct labels, ascending */
+    int U;
+} oe_decoding_graph;
+typedef struct oe_ctc_graph_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_decoding_graph* graph;
+    int normalized, max_trav;
+    float* score; int* frames; int* arcs; float* path_logp;
+    int* n_trav; int* trav_arc; int* trav_start; int* trav_end; float* trav_logp;
+    void* workspace;
+} oe_ctc_graph_args;
+size_t oe_ctc_graph_workspace_bytes(int B, int T, int U, int Q, int A);
+int oe_ctc_graph(const oe_ctc_graph_args* args, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

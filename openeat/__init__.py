@@ -12,7 +12,7 @@ _SUBMODULES = [
     "modules.decoder_layer", "modules.embedding", "modules.encoder", "modules.encoder_layer",
     "modules.label_smoothing_loss", "modules.positionwise_feed_forward", "modules.subsampling", "modules.swish",
     "dataset", "dataset.audio_processor", "dataset.dataset", "dataset.sampler",
-    "utils", "utils.align", "utils.checkpoint", "utils.cmvn", "utils.common", "utils.context_graph", "utils.error_rate", "utils.executor", "utils.mask", "utils.scheduler",
+    "utils", "utils.align", "utils.checkpoint", "utils.cmvn", "utils.common", "utils.context_graph", "utils.decoding_graph", "utils.error_rate", "utils.executor", "utils.mask", "utils.scheduler",
 ]
 for _name in _SUBMODULES:
     _mod = importlib.import_module("openeat_amd." + _name)

@@ -229,6 +229,22 @@ class CtcKwsArgs(C.Structure):
                 ("best_start", c_fp), ("best_end", c_fp), ("best_score", c_fp), ("workspace", c_fp)]
 
 
+class DecodingGraph(C.Structure):
+    """oe_decoding_graph (include/openeat_hip.h); filled by decoding_graph."""
+    _fields_ = [("Q", C.c_int), ("A", C.c_int), ("in_ptr", c_fp), ("src", c_fp), ("dst", c_fp), ("label", c_fp), ("col", c_fp),
+                ("w", c_fp), ("final", c_fp), ("cols", c_fp), ("U", C.c_int)]
+
+
+class CtcGraphArgs(C.Structure):
+    """oe_ctc_graph_args (include/openeat_hip.h); filled by ops.ctc_graph_decode.  A struct assigned through C.pointer to graph
+    stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("graph", C.POINTER(DecodingGraph)), ("normalized", C.c_int), ("max_trav", C.c_int),
+                ("score", c_fp), ("frames", c_fp), ("arcs", c_fp), ("path_logp", c_fp),
+                ("n_trav", c_fp), ("trav_arc", c_fp), ("trav_start", c_fp), ("trav_end", c_fp), ("trav_logp", c_fp),
+                ("workspace", c_fp)]
+
+
 I, L, F, D, P, U64, SZ =C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
@@ -277,6 +293,8 @@ _SIGNATURES = {
     "oe_ctc_segment": (I, [C.POINTER(CtcSegmentArgs), P]),
     "oe_ctc_kws_workspace_bytes": (SZ, [I, I, I]),
     "oe_ctc_kws": (I, [C.POINTER(CtcKwsArgs), P]),
+    "oe_ctc_graph_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "oe_ctc_graph": (I, [C.POINTER(CtcGraphArgs), P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),
@@ -612,6 +630,16 @@ def keyword_set(keywords, device) -> KeywordSet:
     q = KeywordSet(cols.data_ptr(), int(cols.shape[0]), kw_col.data_ptr(), klens.data_ptr(), thr.data_ptr(), int(kw_col.shape[0]),
                    int(kw_col.shape[1]))
     q.owner = keywords                                             # the pointers live as long as the struct
+    return q
+
+
+def decoding_graph(graph, device) -> DecodingGraph:
+    """The oe_decoding_graph of `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph, with its tables on `device` (the
+    graph keeps them, the struct keeps the graph)."""
+    in_ptr, src, dst, label, col, w, final, cols = graph.device_tables(device)
+    q = DecodingGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
+                      col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]))
+    q.owner = graph                                                # the pointers live as long as the struct
     return q
 
 

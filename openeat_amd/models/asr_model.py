@@ -474,6 +474,29 @@ class ASRModel(torch.nn.Module):
         return hit_records(keywords, n.view(B, K).tolist(), s.view(shape).tolist(), e.view(shape).tolist(), sc.view(shape).tolist(), times)
 
     @torch.no_grad()
+    def ctc_graph_search(self, features: torch.Tensor, features_length: torch.Tensor, graph, window: Optional[int] = None,
+                         margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10):
+        """Grammar-constrained CTC decoding (the reference has none; semantics in include/openeat_hip.h, oe_ctc_graph): the
+        best path of each utterance through `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph - the output is in the
+        grammar by construction, or the utterance is infeasible.  Logits by ctc_logits_windowed (window None: one plain pass),
+        recursion, back-trace and traversal list on the device, one D2H copy of the results.  Returns a GraphResult per
+        utterance (tokens, traversals and outputs with their frame spans, score, feasible; with_times adds seconds)."""
+        from openeat_amd.utils.decoding_graph import DecodingGraph, graph_results
+        if not isinstance(graph, DecodingGraph):
+            raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+        assert features.shape[0] == features_length.shape[0]
+        logits, lens = self.ctc_logits_windowed(features, features_length, window, margin)
+        score, _, _, _, n_trav, arc, start, end, logp = ops.ctc_graph_decode(logits, lens, graph)
+        B, M = arc.shape
+        packed = torch.cat([score.double(), n_trav.double(), arc.double().flatten(), start.double().flatten(), end.double().flatten(),
+                            logp.double().flatten()]).cpu()
+        sc, n, (a, s, e, lg) = packed[:B], packed[B: 2 * B], packed[2 * B:].split(B * M)
+        rate = self.encoder.embed.subsampling_rate
+        times = (lambda t0, t1: frame_times(t0, t1, rate, frame_shift_ms)) if with_times else None
+        return graph_results(graph, sc.tolist(), n.tolist(), a.view(B, M).tolist(), s.view(B, M).tolist(), e.view(B, M).tolist(),
+                             lg.view(B, M).tolist(), times)
+
+    @torch.no_grad()
     def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],
                           margin: int = 16):
         """The per-frame top-`beam_size` CTC log-probabilities of whole recordings, window by window: a generator over

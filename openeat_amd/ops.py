@@ -2446,6 +2446,56 @@ def ctc_keyword_search(logits, hlens, keywords, max_hits=8, normalized=False, ma
     return outs
 
 
+def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, workspace_cap=1 << 30):
+    """Grammar-constrained CTC decoding (oe_ctc_graph; semantics in include/openeat_hip.h): logits (B, T, V) float32 (raw, or
+    log-probabilities with normalized=True), hlens (B), graph an openeat_amd.utils.decoding_graph.DecodingGraph -> device
+    tensors (score (B) float32, frames, arcs (B, T) int32, path_logp (B, T) float32, n_trav (B) int32, trav_arc, trav_start,
+    trav_end (B, max_trav) int32, trav_logp (B, max_trav) float32).  max_trav None: T, which no path exceeds.  The workspace
+    is 4 * T * (U + 1 + Q + ceil(A / 4)) bytes per utterance; where that exceeds workspace_cap for the batch the utterances -
+    they are independent - run in consecutive groups of as many as fit (at least one), one workspace reused: exactly the
+    results of one call."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph
+    if not isinstance(graph, DecodingGraph):
+        raise TypeError(f"ctc_graph_decode: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    logits = _chk(logits, "ctc_graph_decode")
+    if logits.dim() != 3:
+        raise ValueError(f"ctc_graph_decode: logits must be (B, T, V), got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    B, T, V = logits.shape
+    dev = logits.device
+    max_trav = T if max_trav is None else int(max_trav)
+    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
+    per_utt = hip.lib().oe_ctc_graph_workspace_bytes(1, T, U, Q, A) if B >= 1 else 0
+    if per_utt == 0 or max_trav < 1 or U >= V:
+        raise ValueError(f"ctc_graph_decode: B={B} T={T} max_trav={max_trav} U={U} V={V} Q={Q} A={A} outside 1 <= B, 1 <= T <= 2^20, "
+                         "1 <= max_trav, 1 <= U < V, 1 <= Q <= 8064, 1 <= A <= 16384 (a graph without arcs has no device form)")
+    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    frames = torch.empty(B, T, dtype=torch.int32, device=dev)
+    arcs = torch.empty(B, T, dtype=torch.int32, device=dev)
+    path_logp = torch.empty(B, T, dtype=torch.float32, device=dev)
+    n_trav = torch.empty(B, dtype=torch.int32, device=dev)
+    trav_arc = torch.empty(B, max_trav, dtype=torch.int32, device=dev)
+    trav_start = torch.empty(B, max_trav, dtype=torch.int32, device=dev)
+    trav_end = torch.empty(B, max_trav, dtype=torch.int32, device=dev)
+    trav_logp = torch.empty(B, max_trav, dtype=torch.float32, device=dev)
+    outs = (score, frames, arcs, path_logp, n_trav, trav_arc, trav_start, trav_end, trav_logp)
+    group = min(max(int(workspace_cap) // per_utt, 1), B)
+    ws = torch.empty(per_utt * group, dtype=torch.uint8, device=dev)
+    g = hip.decoding_graph(graph, dev)
+    for lo in range(0, B, group):
+        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
+        a = hip.CtcGraphArgs()
+        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
+        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+        a.normalized, a.max_trav = int(bool(normalized)), max_trav
+        a.score, a.frames, a.arcs, a.path_logp = (t[lo:].data_ptr() for t in outs[:4])
+        a.n_trav, a.trav_arc, a.trav_start, a.trav_end, a.trav_logp = (t[lo:].data_ptr() for t in outs[4:])
+        a.workspace = ws.data_ptr()
+        hip.check(hip.lib().oe_ctc_graph(hip.C.byref(a), hip.stream()), "oe_ctc_graph")
+    return outs
+
+
 def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
     """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
     openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:
