@@ -607,6 +607,119 @@ typedef struct oe_ctc_graph_args {
 size_t oe_ctc_graph_workspace_bytes(int B, int T, int U, int Q, int A);
 int oe_ctc_graph(const oe_ctc_graph_args* args, void* stream);
 
+/* Graph CTC likelihood on device: the sum half of oe_ctc_graph.  logZ = log of the sum, over every path the graph accepts and
+ * every CTC alignment of it, of the path's probability times exp(its weights), and its gradient with respect to raw logits
+ * (what k2 / WeNet users know as a graph CTC loss; the reference has none).  With normalised posteriors and zero weights
+ * exp(logZ) is P(the utterance's labelling is in the grammar), and exp(oe_ctc_graph's score - logZ) is the best path's posterior.
+ *   The graph, the node states n[q] and arc states r[a], lp, Tb and the clamping of labels and indices are oe_ctc_graph's; every
+ *   "best of" becomes a log-sum-exp (LSE).  Before frame 0, n[0] = 0 and every other state is unreachable; for t = 0 .. Tb-1:
+ *     r_t[a] = lp[t,label[a]] + LSE( r_{t-1}[a],  n_{t-1}[src[a]] + w[a],
+ *                                    r_{t-1}[a'] + w[a] for every a' with dst[a'] == src[a] and label[a'] != label[a] )
+ *     n_t[q] = lp[t,0]        + LSE( n_{t-1}[q],  r_{t-1}[a'] for every a' with dst[a'] == q )
+ *     logZ   = LSE( n_{Tb-1}[q] + final[q] over q,  r_{Tb-1}[a] + final[dst[a]] over a )
+ *   Parallel arcs of one label are separate paths and both count (the weighted-automaton sum).  Tb == 0 or no final state
+ *   reachable: the utterance is infeasible, its logp is -inf exactly and its gradient rows are exact zeros.  On
+ *   DecodingGraph.linear(tokens) logZ is the CTC log-likelihood of tokens (oe_ctc_nbest_score's); on a token loop with raw
+ *   logits every labelling has one state sequence, so logZ = 0 and the gradient is zero.
+ *   Gradient (raw logits only).  beta_{Tb-1}[n q] = final[q], beta_{Tb-1}[r a] = final[dst[a]], and for t = Tb-2 .. 0
+ *     beta_t[r a] = LSE( lp[t+1,label a] + beta_{t+1}[r a],  lp[t+1,0] + beta_{t+1}[n dst[a]],
+ *                        w[a''] + lp[t+1,label a''] + beta_{t+1}[r a''] for a'' with src[a''] == dst[a], label[a''] != label[a] )
+ *     beta_t[n q] = LSE( lp[t+1,0] + beta_{t+1}[n q],  w[a''] + lp[t+1,label a''] + beta_{t+1}[r a''] for a'' with src[a''] == q )
+ *   occ[t,v] = the sum over the states s of label v (node states count for v = 0) of exp(alpha_t[s] + beta_t[s] - logZ); each
+ *   row of occ sums to 1.  dlogits[b,t,v] = g[b] * (occ[b,t,v] - softmax(logits[b,t,:])[v]) for t < Tb, the gradient of
+ *   sum_b g[b] * logp[b]; rows t >= Tb and every row of an infeasible utterance are exact zeros; columns >= V are never
+ *   written; g of an infeasible utterance is not read into any result (it may be NaN), as in oe_ctc_nbest_grad.
+ *   oe_graph_set: G graphs concatenated (built by openeat_amd/utils/decoding_graph.py, GraphSet; host memory read during the
+ *   call only, its pointers device pointers, every table int32 but w and final).  Graph i owns the nodes node_off[i] ..
+ *   node_off[i+1]-1 and the arcs arc_off[i] .. arc_off[i+1]-1 of the concatenated tables; every index stored in a table is
+ *   local to its graph.  A table of n+1 entries per graph (n = its nodes, arcs or groups) lies at node_off[i] + i or
+ *   arc_off[i] + i.  The set has ONE cols / U, the union of its graphs' labels, so one compact lp row serves every utterance.
+ *     the tables of oe_decoding_graph: in_ptr (Q+G), src, dst, label, col, w (A), final (Q), cols (U);
+ *     in-groups: the arcs into a node ordered by (col, id) are in_perm (A); a group is a maximal run of one col;
+ *       in_gptr (Q+G): the groups of node q are in_gptr[q] .. in_gptr[q+1]-1; in_gstart (A+G): group g holds
+ *       in_perm[in_gstart[g] .. in_gstart[g+1]-1]; in_xg (A): the in-group of src[a] that carries col[a], or -1;
+ *     out-groups, the mirror image over the arcs leaving a node: out_perm, out_gptr, out_gstart, and out_xg (A): the
+ *       out-group of dst[a] that carries col[a], or -1;
+ *     by column: col_perm (A) the arcs ordered by (col, id), col_ptr (G * (U+1)): graph i's arcs of column k are
+ *       col_perm[col_ptr[i*(U+1)+k] .. col_ptr[i*(U+1)+k+1]-1];
+ *     inv (n_inv): inv[v] = 0 for v = 0, 1 + k where cols[k] == v, -1 otherwise (a label v >= V takes no gradient);
+ *     Q, A the totals, Qmax / Amax the largest graph's.
+ *   graph_of (B) int32 on the device names each utterance's graph, held to [0, G); NULL: graph 0 for all.
+ *   oe_ctc_graph_logp: logp (B) float32.  workspace: oe_ctc_graph_logp_workspace_bytes(B,T,U,Qmax,Amax) = 4*B*T*(U+1), the lp
+ *   rows of oe_ctc_kws; the score keeps no other per-frame state.
+ *   oe_ctc_graph_logp_grad: g (B) float32 in; dlogits (B, T, ldv) out, which may not alias logits; logp (B) out or NULL,
+ *   bit-identical to oe_ctc_graph_logp's.  normalized != 0 is an error.  It runs the forward recursion itself and keeps alpha in
+ *   its workspace - nothing is handed over from the score call, so a caller short of memory runs utterance groups in both
+ *   directions with one workspace: oe_ctc_graph_logp_grad_workspace_bytes(B,T,U,Qmax,Amax) = lp and occ rows
+ *   (2 * 4*B*T*(U+1)), a row log-sum-exp (4*B*T), logZ (8*B) and alpha (8*B*T*(Qmax+Amax)), each part rounded up to 16 bytes.
+ *   Numbers: the state is float64 in the log2 domain with a finite "log 0" (-1e30), exp / log are float32 on differences, the
+ *   scheme of oe_ctc_loss_fused above 248 frames; there is no float32 path.  "All arcs into src[a] but those of label[a]" is
+ *   never a subtraction: per node a forward sweep over its groups leaves the prefix LSE in a slot per group and a backward sweep
+ *   combines the suffix into it (a wave with a log-semiring scan for a node of more than 32 arcs), O(A + Q) per frame.
+ *   Against the float64 restatement (tests/ctc_graph_logp_ref.py): logp rtol 1e-4 / atol 1e-3, gradient rtol 2e-3 / atol
+ *   2e-5 * |g[b]|, the tolerances of oe_ctc_loss_fused.  Worst observed (tests/test_ctc_graph_logp_gpu.py, one MI355X): 0.0008 of
+ *   the logp tolerance and 0.033 of the gradient's (a token loop, V = 300); 0.0002 / 0.0024 at T = 600 with logp = -1724.
+ *   Limits: 1 <= B, 1 <= T <= 2^20, V > 1, ldv >= V, 1 <= U < V, 1 <= G, 1 <= Qmax <= OE_CTC_GRAPH_LOGP_MAX_NODES,
+ *   1 <= Amax <= OE_CTC_GRAPH_LOGP_MAX_ARCS: one workgroup holds 24 bytes per arc (r, and two values per group) and 8 per node
+ *   in the 160 KiB of LDS (24 * 5120 + 8 * 4096 = 152 KiB, the rest its lists and reduction slots).  Anything else, any NULL
+ *   required pointer (logits, hlens, set and its tables, logp for the score; g, dlogits for the gradient; workspace), a
+ *   workspace not 16-byte aligned, and dlogits == logits are reported through oe_last_error before any launch, with the outputs
+ *   untouched.  The size functions return 0 outside the limits.
+ * Launches: the row pass of oe_ctc_kws; one workgroup per utterance (score: the forward recursion; gradient: forward, beta and
+ * the occupancies); for the gradient one dense pass over the dlogits rows.  Every sum runs in a fixed order: results are
+ * bit-identical from run to run, logp[b] and dlogits[b] depend on utterance b alone.  No float atomics, no workgroup waits for
+ * another; no allocation, no host read, no host-side state: capturable. */
+#define OE_CTC_GRAPH_LOGP_MAX_NODES 4096
+#define OE_CTC_GRAPH_LOGP_MAX_ARCS 5120
+typedef struct oe_graph_set {
+    int G, Q, A, U, Qmax, Amax, n_inv;
+    const int* node_off;  /* (G+1) */
+    const int* arc_off;   /* (G+1) */
+    const int* in_ptr;    /* (Q+G) */
+    const int* src;       /* (A) */
+    const int* dst;       /* (A) */
+    const int* label;     /* (A) */
+    const int* col;       /* (A) index of label[a] into cols */
+    const float* w;       /* (A) */
+    const float* final;   /* (Q) -inf: not final */
+    const int* cols;      /* (U) the distinct labels of all graphs, ascending */
+    const int* in_gptr;   /* (Q+G) */
+    const int* in_gstart; /* (A+G) */
+    const int* in_perm;   /* (A) */
+    const int* in_xg;     /* (A) */
+    const int* out_gptr;  /* (Q+G) */
+    const int* out_gstart;/* (A+G) */
+    const int* out_perm;  /* (A) */
+    const int* out_xg;    /* (A) */
+    const int* col_ptr;   /* (G*(U+1)) */
+    const int* col_perm;  /* (A) */
+    const int* inv;       /* (n_inv) */
+} oe_graph_set;
+typedef struct oe_ctc_graph_logp_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_graph_set* set;
+    const int* graph_of;
+    int normalized;
+    float* logp;
+    void* workspace;
+} oe_ctc_graph_logp_args;
+typedef struct oe_ctc_graph_logp_grad_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_graph_set* set;
+    const int* graph_of;
+    int normalized;
+    const float* g;
+    float* dlogits;
+    float* logp;
+    void* workspace;
+} oe_ctc_graph_logp_grad_args;
+size_t oe_ctc_graph_logp_workspace_bytes(int B, int T, int U, int Qmax, int Amax);
+size_t oe_ctc_graph_logp_grad_workspace_bytes(int B, int T, int U, int Qmax, int Amax);
+int oe_ctc_graph_logp(const oe_ctc_graph_logp_args* args, void* stream);
+int oe_ctc_graph_logp_grad(const oe_ctc_graph_logp_grad_args* args, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

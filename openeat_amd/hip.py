@@ -245,6 +245,30 @@ class CtcGraphArgs(C.Structure):
                 ("workspace", c_fp)]
 
 
+class GraphSet(C.Structure):
+    """oe_graph_set (include/openeat_hip.h); filled by graph_set."""
+    _fields_ = [("G", C.c_int), ("Q", C.c_int), ("A", C.c_int), ("U", C.c_int), ("Qmax", C.c_int), ("Amax", C.c_int), ("n_inv", C.c_int),
+                ("node_off", c_fp), ("arc_off", c_fp), ("in_ptr", c_fp), ("src", c_fp), ("dst", c_fp), ("label", c_fp), ("col", c_fp),
+                ("w", c_fp), ("final", c_fp), ("cols", c_fp), ("in_gptr", c_fp), ("in_gstart", c_fp), ("in_perm", c_fp), ("in_xg", c_fp),
+                ("out_gptr", c_fp), ("out_gstart", c_fp), ("out_perm", c_fp), ("out_xg", c_fp), ("col_ptr", c_fp), ("col_perm", c_fp),
+                ("inv", c_fp)]
+
+
+class CtcGraphLogpArgs(C.Structure):
+    """oe_ctc_graph_logp_args (include/openeat_hip.h); filled by ops.ctc_graph_logp.  A struct assigned through C.pointer to set
+    stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("set", C.POINTER(GraphSet)), ("graph_of", c_fp), ("normalized", C.c_int),
+                ("logp", c_fp), ("workspace", c_fp)]
+
+
+class CtcGraphLogpGradArgs(C.Structure):
+    """oe_ctc_graph_logp_grad_args (include/openeat_hip.h); filled by ops.ctc_graph_logp's backward."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("set", C.POINTER(GraphSet)), ("graph_of", c_fp), ("normalized", C.c_int),
+                ("g", c_fp), ("dlogits", c_fp), ("logp", c_fp), ("workspace", c_fp)]
+
+
 I, L, F, D, P, U64, SZ =C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
@@ -295,6 +319,10 @@ _SIGNATURES = {
     "oe_ctc_kws": (I, [C.POINTER(CtcKwsArgs), P]),
     "oe_ctc_graph_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph": (I, [C.POINTER(CtcGraphArgs), P]),
+    "oe_ctc_graph_logp_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "oe_ctc_graph_logp_grad_workspace_bytes": (SZ, [I, I, I, I, I]),
+    "oe_ctc_graph_logp": (I, [C.POINTER(CtcGraphLogpArgs), P]),
+    "oe_ctc_graph_logp_grad": (I, [C.POINTER(CtcGraphLogpGradArgs), P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),
@@ -640,6 +668,19 @@ def decoding_graph(graph, device) -> DecodingGraph:
     q = DecodingGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
                       col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]))
     q.owner = graph                                                # the pointers live as long as the struct
+    return q
+
+
+def graph_set(gset, device) -> GraphSet:
+    """The oe_graph_set of `gset`, an openeat_amd.utils.decoding_graph.GraphSet, with its tables on `device` (the set keeps
+    them, the struct keeps the set)."""
+    t = gset.device_tables(device)
+    q = GraphSet()
+    q.G, q.Q, q.A, q.U = gset.num_graphs, int(t["final"].shape[0]), int(t["src"].shape[0]), int(t["cols"].shape[0])
+    q.Qmax, q.Amax, q.n_inv = gset.Qmax, gset.Amax, int(t["inv"].shape[0])
+    for name in gset.NAMES:
+        setattr(q, name, t[name].data_ptr())
+    q.owner = gset                                                 # the pointers live as long as the struct
     return q
 
 

@@ -208,6 +208,32 @@ class ASRModel(torch.nn.Module):
         return loss, dict(loss_mwer=loss_mwer.detach(), loss_base=base.detach(), acc=acc, expected_errors=expected.detach(),
                           logp=logp.detach(), errors=errors, prefixes=prefixes, plen=plen)
 
+    def ctc_graph_loss(self, features: torch.Tensor, features_length: torch.Tensor, graphs, graph_of=None,
+                       targets: Optional[torch.Tensor] = None, targets_length: Optional[torch.Tensor] = None):
+        """Training against decoding graphs (what k2 / WeNet users know as a graph CTC loss; the reference trains on one
+        spelling only): `graphs` a DecodingGraph, a list of them or a GraphSet (openeat_amd.utils.decoding_graph; transcripts
+        with alternatives come from DecodingGraph.from_alternatives), graph_of (B) the graph of each utterance (None: graph 0
+        for all).  One encoder pass; logp = ops.ctc_graph_logp on the CTC logits (semantics in include/openeat_hip.h,
+        oe_ctc_graph_logp), and loss_ctc = -(the sum of logp over the feasible utterances) / B, the zero_infinity convention
+        of the CTC head.  With `targets` (the canonical spelling) and ctc_weight < 1 the attention losses are computed on
+        them and combined as in forward(); otherwise the result is the CTC term alone.  Eager only; no host read.
+        -> loss, info: device tensors logp (B), feasible (B) bool, acc (None without the attention term)."""
+        assert features.shape[0] == features_length.shape[0]
+        ops.predrop_clear()
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        logits = self.ctc.logits(encoder_out)
+        logp = ops.ctc_graph_logp(logits, encoder_out_lens, graphs, graph_of)
+        feasible = torch.isfinite(logp.detach())
+        loss_ctc = -torch.where(feasible, logp, torch.zeros_like(logp)).sum() / logp.shape[0]
+        acc = None
+        loss = loss_ctc
+        if targets is not None and self.ctc_weight < 1:
+            assert targets_length is not None and targets.shape[0] == targets_length.shape[0] == features.shape[0]
+            l_loss, r_loss, acc = self._att_losses(encoder_out, encoder_mask, targets, targets_length)
+            loss = self._joint_loss(loss_ctc, l_loss, r_loss)
+        return loss, dict(logp=logp.detach(), feasible=feasible, acc=acc)
+
     @torch.no_grad()
     def ctc_nbest(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int):
         """The CTC n-best list of every utterance with each entry's EXACT CTC log-likelihood beside the beam's score (which
@@ -475,12 +501,15 @@ class ASRModel(torch.nn.Module):
 
     @torch.no_grad()
     def ctc_graph_search(self, features: torch.Tensor, features_length: torch.Tensor, graph, window: Optional[int] = None,
-                         margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10):
+                         margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10, posterior: bool = False):
         """Grammar-constrained CTC decoding (the reference has none; semantics in include/openeat_hip.h, oe_ctc_graph): the
         best path of each utterance through `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph - the output is in the
         grammar by construction, or the utterance is infeasible.  Logits by ctc_logits_windowed (window None: one plain pass),
         recursion, back-trace and traversal list on the device, one D2H copy of the results.  Returns a GraphResult per
-        utterance (tokens, traversals and outputs with their frame spans, score, feasible; with_times adds seconds)."""
+        utterance (tokens, traversals and outputs with their frame spans, score, feasible; with_times adds seconds).
+        posterior=True: each result also carries log_mass, the graph's total log-likelihood on the normalised posteriors
+        (ops.ctc_graph_logp: with zero weights log P(the labelling is in the grammar), a rejection score), and posterior =
+        exp(score - log_mass), the best path's share of it; one more recursion on the device and one more D2H copy."""
         from openeat_amd.utils.decoding_graph import DecodingGraph, graph_results
         if not isinstance(graph, DecodingGraph):
             raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
@@ -493,8 +522,14 @@ class ASRModel(torch.nn.Module):
         sc, n, (a, s, e, lg) = packed[:B], packed[B: 2 * B], packed[2 * B:].split(B * M)
         rate = self.encoder.embed.subsampling_rate
         times = (lambda t0, t1: frame_times(t0, t1, rate, frame_shift_ms)) if with_times else None
-        return graph_results(graph, sc.tolist(), n.tolist(), a.view(B, M).tolist(), s.view(B, M).tolist(), e.view(B, M).tolist(),
-                             lg.view(B, M).tolist(), times)
+        results = graph_results(graph, sc.tolist(), n.tolist(), a.view(B, M).tolist(), s.view(B, M).tolist(), e.view(B, M).tolist(),
+                                lg.view(B, M).tolist(), times)
+        if posterior:
+            mass = ops.ctc_graph_logp(logits, lens, graph).cpu().tolist()
+            for res, m, best in zip(results, mass, score.cpu().tolist()):
+                if res.feasible:
+                    res.log_mass, res.posterior = m, min(math.exp(best - m), 1.0)
+        return results
 
     @torch.no_grad()
     def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],

@@ -2496,6 +2496,96 @@ def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, work
     return outs
 
 
+class CTCGraphLogpFn(torch.autograd.Function):
+    """oe_ctc_graph_logp / oe_ctc_graph_logp_grad (semantics in include/openeat_hip.h): the total log-likelihood of a decoding
+    graph per utterance, differentiable with respect to raw logits.  The utterances run in consecutive groups under the
+    workspace cap, forward and backward, one workspace reused: exactly the results of one call."""
+
+    @staticmethod
+    def forward(ctx, logits, hl32, gset, graph_of, normalized, cap):
+        B, T, V = (int(s) for s in logits.shape)
+        # rows padded beyond V (CTCHeadFn's logits, a [..., :V] view of them) are taken as they are
+        if logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1) and logits.data_ptr() % 4 == 0:
+            buf, ld = logits, int(logits.stride(1))
+        else:
+            buf, ld = logits.contiguous(), V
+        dev = logits.device
+        lib = hip.lib()
+        U, Qmax, Amax = len(gset.cols), gset.Qmax, gset.Amax
+        per_utt = lib.oe_ctc_graph_logp_workspace_bytes(1, T, U, Qmax, Amax)
+        if per_utt == 0 or U >= V:
+            raise ValueError(f"ctc_graph_logp: T={T} U={U} V={V} Qmax={Qmax} Amax={Amax} outside 1 <= T <= 2^20, 1 <= U < V, "
+                             f"Qmax <= {gset.MAX_NODES}, 1 <= Amax <= {gset.MAX_ARCS}")
+        gs = hip.graph_set(gset, dev)
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        group = min(max(int(cap) // per_utt, 1), B)
+        ws = torch.empty(per_utt * group + 16, dtype=torch.uint8, device=dev)
+        for lo in range(0, B, group):
+            a = hip.CtcGraphLogpArgs()
+            a.logits, a.ldv, a.B, a.T, a.V = buf.data_ptr() + 4 * lo * T * ld, ld, min(group, B - lo), T, V
+            a.hlens, a.set = hl32[lo:].data_ptr(), hip.C.pointer(gs)
+            a.graph_of = None if graph_of is None else graph_of[lo:].data_ptr()
+            a.normalized, a.logp, a.workspace = int(bool(normalized)), logp[lo:].data_ptr(), ws.data_ptr()
+            hip.check(lib.oe_ctc_graph_logp(hip.C.byref(a), hip.stream()), "oe_ctc_graph_logp")
+        if ctx.needs_input_grad[0]:
+            if normalized:
+                raise ValueError("ctc_graph_logp: the gradient is with respect to raw logits (normalized=False)")
+            ctx.save_for_backward(buf, hl32, *(() if graph_of is None else (graph_of,)))
+            ctx.cfg = (B, T, V, ld, gset, int(cap))
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        buf, hl32, *rest = ctx.saved_tensors
+        graph_of = rest[0] if rest else None
+        B, T, V, ld, gset, cap = ctx.cfg
+        g = _chk(g, "ctc_graph_logp gradient")
+        dev = buf.device
+        lib = hip.lib()
+        per_utt = lib.oe_ctc_graph_logp_grad_workspace_bytes(1, T, len(gset.cols), gset.Qmax, gset.Amax)
+        gs = hip.graph_set(gset, dev)
+        dlogits = torch.empty(B, T, ld, dtype=torch.float32, device=dev)
+        group = min(max(cap // per_utt, 1), B)
+        ws = torch.empty(lib.oe_ctc_graph_logp_grad_workspace_bytes(group, T, len(gset.cols), gset.Qmax, gset.Amax), dtype=torch.uint8, device=dev)
+        for lo in range(0, B, group):
+            a = hip.CtcGraphLogpGradArgs()
+            a.logits, a.ldv, a.B, a.T, a.V = buf.data_ptr() + 4 * lo * T * ld, ld, min(group, B - lo), T, V
+            a.hlens, a.set = hl32[lo:].data_ptr(), hip.C.pointer(gs)
+            a.graph_of = None if graph_of is None else graph_of[lo:].data_ptr()
+            a.normalized, a.g, a.dlogits, a.logp, a.workspace = 0, g[lo:].data_ptr(), dlogits[lo].data_ptr(), None, ws.data_ptr()
+            hip.check(lib.oe_ctc_graph_logp_grad(hip.C.byref(a), hip.stream()), "oe_ctc_graph_logp_grad")
+        return dlogits[..., :V], None, None, None, None, None
+
+
+def ctc_graph_logp(logits, hlens, graphs, graph_of=None, normalized=False, workspace_cap=1 << 30):
+    """The total log-likelihood of a decoding graph (oe_ctc_graph_logp; semantics in include/openeat_hip.h): logits (B, T, V)
+    float32 (raw, or log-probabilities with normalized=True), hlens (B), graphs a DecodingGraph, a list of them or a GraphSet
+    (openeat_amd.utils.decoding_graph), graph_of (B) the graph of each utterance (None: graph 0 for all) -> logp (B) float32,
+    -inf for an infeasible utterance.  Differentiable with respect to raw logits (an infeasible utterance takes a zero
+    gradient); padded-row views are taken as CTCNbestFn takes them.  Where the workspace exceeds workspace_cap the utterances
+    run in consecutive groups, one workspace reused, forward and backward: exactly the results of one call.  No host read."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph, GraphSet
+    if isinstance(graphs, DecodingGraph) or (isinstance(graphs, (list, tuple)) and all(isinstance(x, DecodingGraph) for x in graphs)):
+        graphs = GraphSet(graphs)
+    if not isinstance(graphs, GraphSet):
+        raise TypeError(f"ctc_graph_logp: graphs must be a DecodingGraph, a list of them or a GraphSet (got {type(graphs).__name__})")
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3):
+        raise TypeError("ctc_graph_logp: logits must be a float32 (B, T, V) CUDA tensor; there is no CPU fallback")
+    pend = _PENDING_LNF.take(logits)
+    if pend is not None:
+        pend.resolve()
+    B = int(logits.shape[0])
+    if B < 1 or tuple(hlens.shape) != (B,):
+        raise ValueError(f"ctc_graph_logp: B={B} utterances need hlens (B), got {tuple(hlens.shape)}")
+    dev = logits.device
+    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
+    if graph_of is not None:
+        graph_of = torch.as_tensor(graph_of).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(graph_of.shape) != (B,):
+            raise ValueError(f"ctc_graph_logp: graph_of must be (B,) = ({B},), got {tuple(graph_of.shape)}")
+    return CTCGraphLogpFn.apply(logits, hl32, graphs, graph_of, bool(normalized), int(workspace_cap))
+
+
 def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
     """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
     openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:

@@ -1,6 +1,6 @@
 """Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode; semantics in
 include/openeat_hip.h, oe_ctc_graph): the token graph with the tables the kernel reads, its builders, and the records made of
-the kernel's outputs.  No kernel here."""
+the kernel's outputs; and GraphSet, the packed form oe_ctc_graph_logp reads.  No kernel here."""
 import math
 from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence
@@ -9,6 +9,8 @@ import numpy as np
 
 MAX_NODES = 8064                 # OE_CTC_GRAPH_MAX_NODES: 12 bytes of LDS per node
 MAX_ARCS = 16384                 # OE_CTC_GRAPH_MAX_ARCS: 4 bytes of LDS per arc
+LOGP_MAX_NODES = 4096            # OE_CTC_GRAPH_LOGP_MAX_NODES: 8 bytes of LDS per node
+LOGP_MAX_ARCS = 5120             # OE_CTC_GRAPH_LOGP_MAX_ARCS: 24 bytes of LDS per arc
 NEG_INF = float("-inf")
 
 
@@ -147,6 +149,57 @@ class DecodingGraph:
         """One node and a self-loop per token 1 .. V-1: unconstrained best-path decoding."""
         return cls(1, [(0, 0, v, 0.0) for v in range(1, int(vocab_size))], {0: 0.0})
 
+    @classmethod
+    def from_alternatives(cls, segments: Sequence[Sequence[Sequence[int]]], weights: Optional[Sequence[Sequence[float]]] = None) -> "DecodingGraph":
+        """A transcript with alternatives (oe_ctc_graph_logp's training graph): `segments` is a sequence of segments, each a
+        list of alternative token sequences ("2" / "two", several pronunciations); an empty alternative makes the segment
+        optional (a filler).  weights[i][j] (default 0) is the weight of alternative j of segment i; a path's weight is the sum
+        over the alternatives it takes.  The sausage is made epsilon-free by classical epsilon removal, from the end so that
+        chains of optional segments work: the arcs leaving the far node of an optional segment are copied to its near node
+        with the skip's weight added, and finality is carried back.  Raises if the whole transcript can be empty, if a
+        segment lists an alternative twice, and if the result exceeds oe_ctc_graph_logp's limits."""
+        segs = [[tuple(int(t) for t in alt) for alt in seg] for seg in segments]
+        if not segs or any(len(seg) == 0 for seg in segs):
+            raise ValueError("DecodingGraph.from_alternatives: at least one segment, each of at least one alternative")
+        wts = [[0.0] * len(seg) for seg in segs] if weights is None else [[float(x) for x in ws] for ws in weights]
+        if len(wts) != len(segs) or any(len(ws) != len(seg) for ws, seg in zip(wts, segs)):
+            raise ValueError("DecodingGraph.from_alternatives: one weight per alternative of every segment")
+        S = len(segs)
+        n = S + 1                                                       # nodes 0 .. S are the sausage's joints
+        out: List[List[tuple]] = [[] for _ in range(S + 1)]             # arcs leaving each joint, (dst, label, weight)
+        inner = []                                                      # arcs inside an alternative's chain
+        skip = [None] * S
+        for i, (seg, ws) in enumerate(zip(segs, wts)):
+            if len(set(seg)) != len(seg):
+                raise ValueError(f"DecodingGraph.from_alternatives: segment {i} lists an alternative twice")
+            for alt, wt in zip(seg, ws):
+                if not alt:
+                    skip[i] = wt
+                    continue
+                q = i
+                for j, t in enumerate(alt):
+                    nxt = i + 1 if j == len(alt) - 1 else n
+                    if nxt == n:
+                        n += 1
+                    if q == i:
+                        out[i].append((nxt, t, wt))
+                    else:
+                        inner.append((q, nxt, t, 0.0))
+                    q = nxt
+        final = {S: 0.0}
+        for i in range(S - 1, -1, -1):
+            if skip[i] is None:
+                continue
+            out[i].extend((d, t, wt + skip[i]) for d, t, wt in out[i + 1])
+            if i + 1 in final:
+                final[i] = final[i + 1] + skip[i]
+        if 0 in final:
+            raise ValueError("DecodingGraph.from_alternatives: the whole transcript can be empty")
+        arcs = [(i, d, t, wt) for i in range(S + 1) for d, t, wt in out[i]] + inner
+        if n > LOGP_MAX_NODES or len(arcs) > LOGP_MAX_ARCS:
+            raise ValueError(f"DecodingGraph.from_alternatives: {n} nodes / {len(arcs)} arcs exceed {LOGP_MAX_NODES} / {LOGP_MAX_ARCS}")
+        return cls(n, arcs, final)
+
     # ---- tables -----------------------------------------------------------------------------------------------------
     def host_tables(self):
         """The arrays device_tables copies, as numpy: (in_ptr, src, dst, label, col, w, final, cols)."""
@@ -188,6 +241,100 @@ class DecodingGraph:
         return any(self.final[q] > NEG_INF for q in nodes) or any(self.final[int(self.dst[a])] > NEG_INF for a in arcs)
 
 
+def _group_tables(node, other, col, Q, U):
+    """The label groups of the arcs at their `node` end (dst: in-groups, src: out-groups): perm (A) = the arcs ordered by
+    (node, col, id); a group is a maximal run of one (node, col); gstart (A+1) = the groups' first positions in perm, padded
+    with A; gptr (Q+1) = the first group of each node; xg (A) = the group of node other[a] that carries col[a], or -1."""
+    A = len(node)
+    perm = np.lexsort((np.arange(A), col, node)).astype(np.int32)
+    key = node[perm].astype(np.int64) * (U + 1) + col[perm]
+    starts = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1]))) if A else np.zeros(0, dtype=np.int64)
+    gstart = np.full(A + 1, A, dtype=np.int32)
+    gstart[:len(starts)] = starts
+    gkey = key[starts]
+    gptr = np.searchsorted(gkey, np.arange(Q + 1, dtype=np.int64) * (U + 1), side="left").astype(np.int32)
+    want = other.astype(np.int64) * (U + 1) + col
+    pos = np.searchsorted(gkey, want)
+    hit = (pos < len(gkey)) & (gkey[np.minimum(pos, max(len(gkey) - 1, 0))] == want) if len(gkey) else np.zeros(A, dtype=bool)
+    xg = np.where(hit, pos, -1).astype(np.int32)
+    return perm, gstart, gptr, xg
+
+
+class GraphSet:
+    """GraphSet(graphs): G DecodingGraphs packed for oe_ctc_graph_logp (oe_graph_set in include/openeat_hip.h).  One `cols`,
+    the union of the graphs' labels, so one compact lp row serves every utterance; node_off / arc_off (G+1) the graphs'
+    ranges in the concatenated tables; every index in a table is local to its graph.  tables: name -> numpy array, the fields
+    of oe_graph_set; `graph_tables(i)` gives graph i's slices."""
+    MAX_NODES, MAX_ARCS = LOGP_MAX_NODES, LOGP_MAX_ARCS
+    PER_NODE = ("final",)                                               # n entries per graph
+    PER_NODE1 = ("in_ptr", "in_gptr", "out_gptr")                       # n + 1
+    PER_ARC = ("src", "dst", "label", "col", "w", "in_perm", "in_xg", "out_perm", "out_xg", "col_perm")
+    PER_ARC1 = ("in_gstart", "out_gstart")
+    NAMES = ("node_off", "arc_off", "in_ptr", "src", "dst", "label", "col", "w", "final", "cols", "in_gptr", "in_gstart", "in_perm",
+             "in_xg", "out_gptr", "out_gstart", "out_perm", "out_xg", "col_ptr", "col_perm", "inv")
+
+    def __init__(self, graphs: Sequence[DecodingGraph]):
+        graphs = [graphs] if isinstance(graphs, DecodingGraph) else list(graphs)
+        if not graphs or not all(isinstance(g, DecodingGraph) for g in graphs):
+            raise TypeError("GraphSet: one or more DecodingGraphs")
+        for i, g in enumerate(graphs):
+            if g.num_nodes > LOGP_MAX_NODES or not 1 <= g.num_arcs <= LOGP_MAX_ARCS:
+                raise ValueError(f"GraphSet: graph {i} has {g.num_nodes} nodes / {g.num_arcs} arcs; the limits are {LOGP_MAX_NODES} "
+                                 f"nodes and 1 .. {LOGP_MAX_ARCS} arcs")
+        self.graphs = graphs
+        self.cols = np.unique(np.concatenate([g.label for g in graphs])).astype(np.int32)
+        U = len(self.cols)
+        parts = {k: [] for k in self.NAMES}
+        for g in graphs:
+            Q, A = g.num_nodes, g.num_arcs
+            col = np.searchsorted(self.cols, g.label).astype(np.int32)
+            in_perm, in_gstart, in_gptr, in_xg = _group_tables(g.dst, g.src, col, Q, U)
+            out_perm, out_gstart, out_gptr, out_xg = _group_tables(g.src, g.dst, col, Q, U)
+            col_perm = np.lexsort((np.arange(A), col)).astype(np.int32)
+            col_ptr = np.searchsorted(col[col_perm], np.arange(U + 1)).astype(np.int32)
+            for k, v in (("in_ptr", g.in_ptr), ("src", g.src), ("dst", g.dst), ("label", g.label), ("col", col), ("w", g.w),
+                         ("final", g.final), ("in_gptr", in_gptr), ("in_gstart", in_gstart), ("in_perm", in_perm), ("in_xg", in_xg),
+                         ("out_gptr", out_gptr), ("out_gstart", out_gstart), ("out_perm", out_perm), ("out_xg", out_xg),
+                         ("col_ptr", col_ptr), ("col_perm", col_perm)):
+                parts[k].append(v)
+        self.num_graphs = len(graphs)
+        self.node_off = np.concatenate(([0], np.cumsum([g.num_nodes for g in graphs]))).astype(np.int32)
+        self.arc_off = np.concatenate(([0], np.cumsum([g.num_arcs for g in graphs]))).astype(np.int32)
+        self.Qmax = max(g.num_nodes for g in graphs)
+        self.Amax = max(g.num_arcs for g in graphs)
+        inv = np.full(int(self.cols.max()) + 1, -1, dtype=np.int32)
+        inv[0] = 0
+        inv[self.cols] = 1 + np.arange(U, dtype=np.int32)
+        self.tables = {k: np.concatenate(v) for k, v in parts.items() if v}
+        self.tables.update(node_off=self.node_off, arc_off=self.arc_off, cols=self.cols, inv=inv)
+        self._device: Dict[object, dict] = {}
+
+    def graph_tables(self, i: int) -> dict:
+        """Graph i's slices of the concatenated tables (col and col_ptr refer to the set's cols)."""
+        q0, q1, a0, a1 = int(self.node_off[i]), int(self.node_off[i + 1]), int(self.arc_off[i]), int(self.arc_off[i + 1])
+        U = len(self.cols)
+        t = {k: self.tables[k][q0:q1] for k in self.PER_NODE}
+        t.update({k: self.tables[k][q0 + i:q1 + i + 1] for k in self.PER_NODE1})
+        t.update({k: self.tables[k][a0:a1] for k in self.PER_ARC})
+        t.update({k: self.tables[k][a0 + i:a1 + i + 1] for k in self.PER_ARC1})
+        t["col_ptr"] = self.tables["col_ptr"][i * (U + 1):(i + 1) * (U + 1)]
+        return t
+
+    def device_tables(self, device) -> dict:
+        """tables on `device`; made once per device and kept."""
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise TypeError(f"GraphSet: device tables live on a GPU (got {device})")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._device.get(device)
+        if t is None:
+            t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in self.tables.items()}
+            self._device[device] = t
+        return t
+
+
 @dataclass
 class GraphResult:
     """One utterance decoded through a DecodingGraph.  tokens: the path collapsed (a label per arc traversal);  traversals:
@@ -195,13 +342,17 @@ class GraphResult:
     exp(logp / frames)};  outputs: the traversals of arcs that carry an output, each {"output", "start_frame", "end_frame",
     "confidence"} - the span from the end of the previous output to this arc's last frame, the confidence over the traversals in
     it - and with times "start_s" / "end_s";  score: the path's value, weights and final weight included (-inf if infeasible);
-    truncated: more traversals than were asked for, only the first are listed."""
+    truncated: more traversals than were asked for, only the first are listed;  log_mass, posterior (ctc_graph_search with
+    posterior=True, else None): the graph's total log-likelihood on the normalised posteriors (oe_ctc_graph_logp) - with zero
+    weights log P(the labelling is in the grammar) - and exp(score - log_mass), the best path's share of it."""
     feasible: bool
     score: float
     tokens: List[int] = field(default_factory=list)
     traversals: List[dict] = field(default_factory=list)
     outputs: List[dict] = field(default_factory=list)
     truncated: bool = False
+    log_mass: Optional[float] = None
+    posterior: Optional[float] = None
 
     @property
     def confidences(self) -> List[float]:
