@@ -607,6 +607,90 @@ typedef struct oe_ctc_graph_args {
 size_t oe_ctc_graph_workspace_bytes(int B, int T, int U, int Q, int A);
 int oe_ctc_graph(const oe_ctc_graph_args* args, void* stream);
 
+/* Beam-pruned CTC decoding over large token graphs on device: oe_ctc_graph's recursion by token passing.  The state lives in
+ * global memory, the states alive after a frame are kept in an active list, and a beam prunes them: a lexicon loop of 10^5
+ * words, a phrase book, a small bigram grammar (what WeNet users mean by TLG decoding).
+ *   oe_ctc_graph's, statement for statement: the graph, the node states n[q] and arc states r[a], lp, Tb and the clamping of
+ *   labels and indices; the tie rule and the end rule; and the arithmetic - per node q the two best incoming values of frame
+ *   t-1 (v1 with its arc id1 and label c1: the best r[a'] into q, lowest id on ties; v2, id2: the best among the arcs whose
+ *   label is not c1), m1 = best(n_{t-1}[q], v1), m2 = best(n_{t-1}[q], v2), the node kept unless the arc is strictly greater;
+ *   then n_t[q] = lp[t,0] + m1[q] and r_t[a] = lp[t,label[a]] + best(r_{t-1}[a], m + w[a]), m = m1[src[a]] if
+ *   c1[src[a]] != label[a] else m2[src[a]], the stay kept unless m + w[a] is strictly greater: float32, the weight added to the
+ *   maximum.
+ *   Beam: beam is a float32, >= 0 or +inf.  After the values of frame t are made, for every t < Tb-1: best_t = the maximum over
+ *   all node and arc states, thr_t = best_t - beam (one float32 subtraction), and every state with a value < thr_t becomes
+ *   unreachable before frame t+1 reads it; a state equal to thr_t survives.  The last frame is not pruned, so pruning never
+ *   removes a final state from the end rule.  There is no histogram pruning (it would need a tie order among equal values).
+ *   Capacity: the survivors of frame t are the states reachable after frame t and its pruning (after the last frame: every
+ *   reachable state); max_active >= 1 is how many of them the call can record per frame.  If the survivor count of some
+ *   frame exceeds max_active the utterance overflows: its outputs are those of an infeasible utterance, and nothing is
+ *   written out of bounds.
+ *   out (device memory): score, frames, arcs, path_logp, n_trav, trav_arc, trav_start, trav_end, trav_logp as oe_ctc_graph, and
+ *        status (B) int32 = OE_CTC_GRAPH_BEAM_OK (0): decoded;  OE_CTC_GRAPH_BEAM_INFEASIBLE (1): Tb == 0 or no final state
+ *        reachable, which pruning may have caused;  OE_CTC_GRAPH_BEAM_OVERFLOW (2);
+ *        peak (B) int32 = the largest per-frame survivor count seen (0 for Tb == 0) or, on overflow, the count at the first
+ *        overflowing frame, so that a caller can size a retry.
+ *   Every output is bit-identical from run to run and those of utterance b depend on utterance b alone; the order in which
+ *   threads append to an active list reaches no output (positions in a list are internal; an arg-max over a list breaks
+ *   ties by state id).
+ *   With beam = +inf, max_active >= Q + A and a graph inside oe_ctc_graph's limits every shared output equals oe_ctc_graph's
+ *   bit for bit, on continuous raw logits too.
+ *   The graph is one struct, oe_beam_graph: the tables of oe_decoding_graph and the out-adjacency, a CSR of the arcs leaving
+ *   each node: out_ptr (Q+1), out_arc (A) = the arc ids ordered by (src, id); host memory read during the call only, its
+ *   pointers device pointers (openeat_amd/utils/decoding_graph.py).  The kernel walks arcs forward from the alive states
+ *   (out_ptr / out_arc) and pushes arc values to their dst; it does not read in_ptr or src.
+ *   Limits: 1 <= B, 1 <= T <= 2^20, V > 1, ldv >= V, 1 <= U < V, max_trav >= 1, max_active >= 1, beam >= 0 (+inf allowed),
+ *   1 <= Q <= OE_CTC_GRAPH_BEAM_MAX_NODES, 1 <= A <= OE_CTC_GRAPH_BEAM_MAX_ARCS.  Anything else, and any NULL required
+ *   pointer (logits, hlens, graph and its ten tables, score, frames, arcs, n_trav, trav_arc, trav_start, trav_end, status, peak,
+ *   workspace), is reported through oe_last_error before any launch, with the outputs untouched.
+ *   workspace: oe_ctc_graph_beam_workspace_bytes(B,T,U,Q,A,max_active) bytes, 16-byte aligned (0 for shapes outside the
+ *   limits).  With M = min(max_active, Q + A) and Q', A', M' = Q, A, M rounded up to a multiple of 4:
+ *     ceil16(4 * B * T * (U + 1))  the lp rows of oe_ctc_kws
+ *     + B * (40 * Q'               per node: two 8-byte push keys, value, stamp, touch stamp, list position; a candidate slot
+ *            + 20 * A'             per arc: value, stamp, list position; a candidate slot
+ *            + 28 * M'             per frame, reused: the touched nodes, the wide ones, and the touched nodes' m1 m2 c1 and the
+ *                                  list positions behind m1 and m2
+ *            + 8 * T * M')         per frame, kept: state id and back-pointer (a position in the previous frame's list) of each
+ *                                  survivor
+ *   No T * Q or T * A term: the graph's size is paid once per utterance (the stamps and keys are zeroed once and are
+ *   afterwards reset by walking the lists), a frame costs O(survivors + their out-arcs).  Utterances are independent, so a
+ *   caller short of memory runs them in groups.
+ * Two launches (the row pass of oe_ctc_kws; one workgroup per utterance).  No workgroup waits for another, no float atomics
+ * (64-bit integer atomicMax on a packed (order-preserving value, inverted arc id) key keeps the tie rule under the push); no
+ * allocation, no host read, no host-side state: capturable. */
+#define OE_CTC_GRAPH_BEAM_MAX_NODES (1 << 20)
+#define OE_CTC_GRAPH_BEAM_MAX_ARCS (1 << 22)
+#define OE_CTC_GRAPH_BEAM_OK 0
+#define OE_CTC_GRAPH_BEAM_INFEASIBLE 1
+#define OE_CTC_GRAPH_BEAM_OVERFLOW 2
+typedef struct oe_beam_graph {
+    int Q, A;
+    const int* in_ptr;    /* (Q+1) the arcs into q are in_ptr[q] .. in_ptr[q+1]-1 */
+    const int* src;       /* (A) */
+    const int* dst;       /* (A) ascending */
+    const int* label;     /* (A) */
+    const int* col;       /* (A) index of label[a] into cols */
+    const float* w;       /* (A) */
+    const float* final;   /* (Q) -inf: not final */
+    const int* cols;      /* (U) the distinct labels, ascending */
+    int U;
+    const int* out_ptr;   /* (Q+1) the arcs leaving q are out_arc[out_ptr[q] .. out_ptr[q+1]-1] */
+    const int* out_arc;   /* (A) arc ids ordered by (src, id) */
+} oe_beam_graph;
+typedef struct oe_ctc_graph_beam_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_beam_graph* graph;
+    int normalized, max_trav, max_active;
+    float beam;
+    float* score; int* frames; int* arcs; float* path_logp;
+    int* n_trav; int* trav_arc; int* trav_start; int* trav_end; float* trav_logp;
+    int* status; int* peak;
+    void* workspace;
+} oe_ctc_graph_beam_args;
+size_t oe_ctc_graph_beam_workspace_bytes(int B, int T, int U, int Q, int A, int max_active);
+int oe_ctc_graph_beam(const oe_ctc_graph_beam_args* args, void* stream);
+
 /* Graph CTC likelihood on device: the sum half of oe_ctc_graph.  logZ = log of the sum, over every path the graph accepts and
  * every CTC alignment of it, of the path's probability times exp(its weights), and its gradient with respect to raw logits
  * (what k2 / WeNet users know as a graph CTC loss; the reference has none).  With normalised posteriors and zero weights

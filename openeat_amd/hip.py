@@ -245,6 +245,26 @@ class CtcGraphArgs(C.Structure):
                 ("workspace", c_fp)]
 
 
+CTC_GRAPH_BEAM_OK, CTC_GRAPH_BEAM_INFEASIBLE, CTC_GRAPH_BEAM_OVERFLOW = 0, 1, 2      # OE_CTC_GRAPH_BEAM_*: oe_ctc_graph_beam's status
+
+
+class BeamGraph(C.Structure):
+    """oe_beam_graph (include/openeat_hip.h); filled by beam_graph."""
+    _fields_ = [("Q", C.c_int), ("A", C.c_int), ("in_ptr", c_fp), ("src", c_fp), ("dst", c_fp), ("label", c_fp), ("col", c_fp),
+                ("w", c_fp), ("final", c_fp), ("cols", c_fp), ("U", C.c_int), ("out_ptr", c_fp), ("out_arc", c_fp)]
+
+
+class CtcGraphBeamArgs(C.Structure):
+    """oe_ctc_graph_beam_args (include/openeat_hip.h); filled by ops.ctc_graph_beam_decode.  A struct assigned through C.pointer
+    to graph stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("graph", C.POINTER(BeamGraph)), ("normalized", C.c_int), ("max_trav", C.c_int),
+                ("max_active", C.c_int), ("beam", C.c_float),
+                ("score", c_fp), ("frames", c_fp), ("arcs", c_fp), ("path_logp", c_fp),
+                ("n_trav", c_fp), ("trav_arc", c_fp), ("trav_start", c_fp), ("trav_end", c_fp), ("trav_logp", c_fp),
+                ("status", c_fp), ("peak", c_fp), ("workspace", c_fp)]
+
+
 class GraphSet(C.Structure):
     """oe_graph_set (include/openeat_hip.h); filled by graph_set."""
     _fields_ = [("G", C.c_int), ("Q", C.c_int), ("A", C.c_int), ("U", C.c_int), ("Qmax", C.c_int), ("Amax", C.c_int), ("n_inv", C.c_int),
@@ -319,6 +339,8 @@ _SIGNATURES = {
     "oe_ctc_kws": (I, [C.POINTER(CtcKwsArgs), P]),
     "oe_ctc_graph_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph": (I, [C.POINTER(CtcGraphArgs), P]),
+    "oe_ctc_graph_beam_workspace_bytes": (SZ, [I, I, I, I, I, I]),
+    "oe_ctc_graph_beam": (I, [C.POINTER(CtcGraphBeamArgs), P]),
     "oe_ctc_graph_logp_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph_logp_grad_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph_logp": (I, [C.POINTER(CtcGraphLogpArgs), P]),
@@ -667,6 +689,18 @@ def decoding_graph(graph, device) -> DecodingGraph:
     in_ptr, src, dst, label, col, w, final, cols = graph.device_tables(device)
     q = DecodingGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
                       col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]))
+    q.owner = graph                                                # the pointers live as long as the struct
+    return q
+
+
+def beam_graph(graph, device) -> BeamGraph:
+    """The oe_beam_graph of `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph: oe_decoding_graph's tables and the
+    out-adjacency on `device` (the graph keeps them, the struct keeps the graph)."""
+    in_ptr, src, dst, label, col, w, final, cols = graph.device_tables(device)
+    out_ptr, out_arc = graph.device_out_tables(device)
+    q = BeamGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
+                  col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]), out_ptr.data_ptr(),
+                  out_arc.data_ptr())
     q.owner = graph                                                # the pointers live as long as the struct
     return q
 

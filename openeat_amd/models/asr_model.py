@@ -501,7 +501,8 @@ class ASRModel(torch.nn.Module):
 
     @torch.no_grad()
     def ctc_graph_search(self, features: torch.Tensor, features_length: torch.Tensor, graph, window: Optional[int] = None,
-                         margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10, posterior: bool = False):
+                         margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10, posterior: bool = False,
+                         beam: Optional[float] = None, max_active: Optional[int] = None, workspace_cap: int = 1 << 30):
         """Grammar-constrained CTC decoding (the reference has none; semantics in include/openeat_hip.h, oe_ctc_graph): the
         best path of each utterance through `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph - the output is in the
         grammar by construction, or the utterance is infeasible.  Logits by ctc_logits_windowed (window None: one plain pass),
@@ -509,13 +510,28 @@ class ASRModel(torch.nn.Module):
         utterance (tokens, traversals and outputs with their frame spans, score, feasible; with_times adds seconds).
         posterior=True: each result also carries log_mass, the graph's total log-likelihood on the normalised posteriors
         (ops.ctc_graph_logp: with zero weights log P(the labelling is in the grammar), a rejection score), and posterior =
-        exp(score - log_mass), the best path's share of it; one more recursion on the device and one more D2H copy."""
-        from openeat_amd.utils.decoding_graph import DecodingGraph, graph_results
+        exp(score - log_mass), the best path's share of it; one more recursion on the device and one more D2H copy.
+        beam None: the dense search (oe_ctc_graph; graphs of at most 8064 nodes and 16384 arcs).  beam a float >= 0 or inf:
+        the token-passing search (oe_ctc_graph_beam), the one a large=True graph has: after every frame but the last the
+        states below the frame's best - beam are dropped, and max_active (default 16384) is how many survivors a frame can
+        record.  An utterance that overflows is run again, alone with the others that did, with max_active doubled (and at
+        least its peak), for as long as one utterance's workspace stays within workspace_cap; after that a RuntimeError names the
+        utterance and its peak.  An utterance may be infeasible through pruning alone; a wider beam is the remedy."""
+        from openeat_amd.utils.decoding_graph import LOGP_MAX_ARCS, LOGP_MAX_NODES, DecodingGraph, graph_results
         if not isinstance(graph, DecodingGraph):
             raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+        if posterior and (graph.num_nodes > LOGP_MAX_NODES or graph.num_arcs > LOGP_MAX_ARCS):
+            raise ValueError(f"posterior=True needs the graph's total likelihood (oe_ctc_graph_logp), which takes at most {LOGP_MAX_NODES} "
+                             f"nodes and {LOGP_MAX_ARCS} arcs; this graph has {graph.num_nodes} / {graph.num_arcs}")
+        if beam is None and max_active is not None:
+            raise ValueError("max_active belongs to the beam search: give a beam (inf for none) with it")
         assert features.shape[0] == features_length.shape[0]
         logits, lens = self.ctc_logits_windowed(features, features_length, window, margin)
-        score, _, _, _, n_trav, arc, start, end, logp = ops.ctc_graph_decode(logits, lens, graph)
+        if beam is None:
+            outs = ops.ctc_graph_decode(logits, lens, graph)
+        else:
+            outs = self._graph_beam_decode(logits, lens, graph, beam, 16384 if max_active is None else int(max_active), int(workspace_cap))
+        score, _, _, _, n_trav, arc, start, end, logp = outs[:9]
         B, M = arc.shape
         packed = torch.cat([score.double(), n_trav.double(), arc.double().flatten(), start.double().flatten(), end.double().flatten(),
                             logp.double().flatten()]).cpu()
@@ -530,6 +546,29 @@ class ASRModel(torch.nn.Module):
                 if res.feasible:
                     res.log_mass, res.posterior = m, min(math.exp(best - m), 1.0)
         return results
+
+    @staticmethod
+    def _graph_beam_decode(logits, lens, graph, beam, max_active, workspace_cap):
+        """ops.ctc_graph_beam_decode with ctc_graph_search's retry: the utterances that overflowed run again with max_active
+        doubled, while one utterance's workspace fits workspace_cap.  One D2H copy of status and peak per round."""
+        B, T, _ = logits.shape
+        outs = ops.ctc_graph_beam_decode(logits, lens, graph, beam, max_active, workspace_cap=workspace_cap)
+        while True:
+            status, peak = torch.stack([outs[9], outs[10]]).cpu().tolist()
+            over = [b for b in range(B) if status[b] == hip.CTC_GRAPH_BEAM_OVERFLOW]
+            if not over:
+                return outs
+            max_active = min(max(2 * max_active, max(peak[b] for b in over)), graph.num_nodes + graph.num_arcs)   # Q + A never overflows
+            need = hip.lib().oe_ctc_graph_beam_workspace_bytes(1, T, len(graph.cols), graph.num_nodes, graph.num_arcs, max_active)
+            if need > workspace_cap:
+                b = max(over, key=lambda i: peak[i])
+                raise RuntimeError(f"ctc_graph_search: utterance {b} keeps {peak[b]} states alive in one frame (peak), and max_active="
+                                   f"{max_active} needs {need} bytes of workspace for one utterance, over workspace_cap={workspace_cap}: "
+                                   "narrow the beam or raise the cap")
+            idx = torch.tensor(over, device=logits.device)
+            part = ops.ctc_graph_beam_decode(logits[idx], lens[idx], graph, beam, max_active, workspace_cap=workspace_cap)
+            for whole, redone in zip(outs, part):
+                whole[idx] = redone
 
     @torch.no_grad()
     def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],

@@ -2496,6 +2496,55 @@ def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, work
     return outs
 
 
+def ctc_graph_beam_decode(logits, hlens, graph, beam, max_active=16384, normalized=False, max_trav=None, workspace_cap=1 << 30):
+    """Beam-pruned CTC decoding over a large token graph (oe_ctc_graph_beam; semantics in include/openeat_hip.h): logits
+    (B, T, V) float32 (raw, or log-probabilities with normalized=True), hlens (B), graph an
+    openeat_amd.utils.decoding_graph.DecodingGraph of either size, beam >= 0 or inf, max_active the survivors a frame can
+    record -> ctc_graph_decode's device tensors and status (B) int32 (0 decoded, 1 infeasible, 2 overflow: more than
+    max_active survivors in some frame) and peak (B) int32 (the largest survivor count, on overflow the overflowing one).
+    The workspace is 4 * T * (U + 1) bytes of rows and 40 Q + 20 A + (28 + 8 T) min(max_active, Q + A) bytes of state per
+    utterance; where that exceeds workspace_cap for the batch the utterances run in consecutive groups of as many as fit (at
+    least one), one workspace reused: exactly the results of one call.  No host read."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph
+    if not isinstance(graph, DecodingGraph):
+        raise TypeError(f"ctc_graph_beam_decode: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    logits = _chk(logits, "ctc_graph_beam_decode")
+    if logits.dim() != 3:
+        raise ValueError(f"ctc_graph_beam_decode: logits must be (B, T, V), got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    B, T, V = logits.shape
+    dev = logits.device
+    max_trav = T if max_trav is None else int(max_trav)
+    beam, max_active = float(beam), int(max_active)
+    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
+    lib = hip.lib()
+    per_utt = lib.oe_ctc_graph_beam_workspace_bytes(1, T, U, Q, A, max_active) if B >= 1 and 1 <= max_active < 1 << 31 else 0
+    if per_utt == 0 or max_trav < 1 or U >= V or not beam >= 0:
+        raise ValueError(f"ctc_graph_beam_decode: B={B} T={T} max_trav={max_trav} max_active={max_active} beam={beam} U={U} V={V} Q={Q} "
+                         f"A={A} outside 1 <= B, 1 <= T <= 2^20, 1 <= max_trav, 1 <= max_active, 0 <= beam, 1 <= U < V, 1 <= Q <= 2^20, "
+                         "1 <= A <= 2^22 (a graph without arcs has no device form)")
+    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    outs = (f32(B), i32(B, T), i32(B, T), f32(B, T), i32(B), i32(B, max_trav), i32(B, max_trav), i32(B, max_trav), f32(B, max_trav),
+            i32(B), i32(B))
+    group = min(max(int(workspace_cap) // per_utt, 1), B)
+    ws = torch.empty(lib.oe_ctc_graph_beam_workspace_bytes(group, T, U, Q, A, max_active), dtype=torch.uint8, device=dev)
+    g = hip.beam_graph(graph, dev)
+    for lo in range(0, B, group):
+        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
+        a = hip.CtcGraphBeamArgs()
+        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
+        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+        a.normalized, a.max_trav, a.max_active, a.beam = int(bool(normalized)), max_trav, max_active, beam
+        a.score, a.frames, a.arcs, a.path_logp = (t[lo:].data_ptr() for t in outs[:4])
+        a.n_trav, a.trav_arc, a.trav_start, a.trav_end, a.trav_logp = (t[lo:].data_ptr() for t in outs[4:9])
+        a.status, a.peak = outs[9][lo:].data_ptr(), outs[10][lo:].data_ptr()
+        a.workspace = ws.data_ptr()
+        hip.check(lib.oe_ctc_graph_beam(hip.C.byref(a), hip.stream()), "oe_ctc_graph_beam")
+    return outs
+
+
 class CTCGraphLogpFn(torch.autograd.Function):
     """oe_ctc_graph_logp / oe_ctc_graph_logp_grad (semantics in include/openeat_hip.h): the total log-likelihood of a decoding
     graph per utterance, differentiable with respect to raw logits.  The utterances run in consecutive groups under the

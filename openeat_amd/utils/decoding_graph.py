@@ -1,6 +1,6 @@
-"""Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode; semantics in
-include/openeat_hip.h, oe_ctc_graph): the token graph with the tables the kernel reads, its builders, and the records made of
-the kernel's outputs; and GraphSet, the packed form oe_ctc_graph_logp reads.  No kernel here."""
+"""Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode, ops.ctc_graph_beam_decode;
+semantics in include/openeat_hip.h, oe_ctc_graph and oe_ctc_graph_beam): the token graph with the tables the kernels read, its
+builders, and the records made of the kernels' outputs; and GraphSet, the packed form oe_ctc_graph_logp reads.  No kernel here."""
 import math
 from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence
@@ -9,13 +9,15 @@ import numpy as np
 
 MAX_NODES = 8064                 # OE_CTC_GRAPH_MAX_NODES: 12 bytes of LDS per node
 MAX_ARCS = 16384                 # OE_CTC_GRAPH_MAX_ARCS: 4 bytes of LDS per arc
+BEAM_MAX_NODES = 1 << 20         # OE_CTC_GRAPH_BEAM_MAX_NODES: the state lives in global memory
+BEAM_MAX_ARCS = 1 << 22          # OE_CTC_GRAPH_BEAM_MAX_ARCS
 LOGP_MAX_NODES = 4096            # OE_CTC_GRAPH_LOGP_MAX_NODES: 8 bytes of LDS per node
 LOGP_MAX_ARCS = 5120             # OE_CTC_GRAPH_LOGP_MAX_ARCS: 24 bytes of LDS per arc
 NEG_INF = float("-inf")
 
 
 class DecodingGraph:
-    """DecodingGraph(num_nodes, arcs, finals, outputs=None): an epsilon-free weighted token graph.  Node 0 is the start.
+    """DecodingGraph(num_nodes, arcs, finals, outputs=None, large=False): an epsilon-free weighted token graph.  Node 0 is the start.
     arcs = (src, dst, label, weight) each, label a token id >= 1 (blank, 0, is never a label), weight a finite natural log;
     finals = {node: weight} or one weight per node with -inf for "not final"; outputs = per arc, in the caller's order, what a
     traversal of the arc emits (a word, a phrase index, anything) or None.  The graph may be non-deterministic and may have
@@ -24,16 +26,21 @@ class DecodingGraph:
     Arcs are kept sorted by dst, stable: within a node the caller's order stays, and an arc's id is its position in that order
     (`order[id]` = the caller's index, `arc_id[caller's index]` = id).  Host tables (oe_decoding_graph): in_ptr (Q+1) int32, the
     arcs into q are in_ptr[q] .. in_ptr[q+1]-1; src, dst, label (A) int32; cols (U) int32 = the distinct labels, ascending;
-    col (A) int32 = the index of label into cols; w (A) float32; final (Q) float32."""
+    col (A) int32 = the index of label into cols; w (A) float32; final (Q) float32; and the out-adjacency oe_beam_graph adds:
+    out_ptr (Q+1) int32, out_arc (A) int32 = the arc ids ordered by (src, id), the arcs leaving q are
+    out_arc[out_ptr[q] .. out_ptr[q+1]-1].
+    large=False: the limits are oe_ctc_graph's (8064 nodes, 16384 arcs: the dense kernel keeps the state in LDS);
+    large=True: those of oe_ctc_graph_beam (2^20 nodes, 2^22 arcs), the only decoder such a graph has."""
 
-    def __init__(self, num_nodes: int, arcs: Sequence[Sequence], finals, outputs: Optional[Sequence] = None):
+    def __init__(self, num_nodes: int, arcs: Sequence[Sequence], finals, outputs: Optional[Sequence] = None, large: bool = False):
         Q = int(num_nodes)
-        if not 1 <= Q <= MAX_NODES:
-            raise ValueError(f"DecodingGraph: {Q} nodes outside 1 .. {MAX_NODES}")
+        max_nodes, max_arcs = self._limits(large)
+        if not 1 <= Q <= max_nodes:
+            raise ValueError(f"DecodingGraph: {Q} nodes outside 1 .. {max_nodes}")
         arcs = [tuple(a) for a in arcs]
         A = len(arcs)
-        if A > MAX_ARCS:
-            raise ValueError(f"DecodingGraph: {A} arcs exceed {MAX_ARCS}")
+        if A > max_arcs:
+            raise ValueError(f"DecodingGraph: {A} arcs exceed {max_arcs}")
         for a in arcs:
             if len(a) != 4:
                 raise ValueError(f"DecodingGraph: an arc is (src, dst, label, weight), got {a}")
@@ -58,23 +65,70 @@ class DecodingGraph:
             raise ValueError("DecodingGraph: a final weight is finite, or -inf for a node that is not final")
         if outputs is not None and len(outputs) != A:
             raise ValueError(f"DecodingGraph: one output per arc ({A}), got {len(outputs)}")
-        self.num_nodes, self.num_arcs = Q, A
-        order = sorted(range(A), key=lambda i: int(arcs[i][1]))        # sorted() is stable
-        self.order = np.asarray(order, dtype=np.int32).reshape(A)
+        self._tables(Q, np.asarray([int(a[0]) for a in arcs], dtype=np.int32).reshape(A), np.asarray([int(a[1]) for a in arcs], dtype=np.int32).reshape(A),
+                     np.asarray([int(a[2]) for a in arcs], dtype=np.int32).reshape(A), np.asarray([float(a[3]) for a in arcs], dtype=np.float32).reshape(A),
+                     fin, outputs, large)
+
+    @staticmethod
+    def _limits(large: bool):
+        return (BEAM_MAX_NODES, BEAM_MAX_ARCS) if large else (MAX_NODES, MAX_ARCS)
+
+    def _tables(self, Q, src, dst, label, w, fin, outputs, large):
+        """The stored form of checked arcs given in the caller's order: sorted by dst, stable, with every table."""
+        A = len(src)
+        self.num_nodes, self.num_arcs, self.large = Q, A, bool(large)
+        self.order = np.argsort(dst, kind="stable").astype(np.int32)
         self.arc_id = np.empty(A, dtype=np.int32)
         self.arc_id[self.order] = np.arange(A, dtype=np.int32)
-        self.src = np.asarray([int(arcs[i][0]) for i in order], dtype=np.int32).reshape(A)
-        self.dst = np.asarray([int(arcs[i][1]) for i in order], dtype=np.int32).reshape(A)
-        self.label = np.asarray([int(arcs[i][2]) for i in order], dtype=np.int32).reshape(A)
-        self.w = np.asarray([float(arcs[i][3]) for i in order], dtype=np.float32).reshape(A)
+        self.src, self.dst, self.label, self.w = src[self.order], dst[self.order], label[self.order], w[self.order]
         self.final = fin
-        self.outputs = [None] * A if outputs is None else [outputs[i] for i in order]
+        self.outputs = [None] * A if outputs is None else [outputs[i] for i in self.order.tolist()]
         self.in_ptr = np.zeros(Q + 1, dtype=np.int32)
         np.cumsum(np.bincount(self.dst, minlength=Q), out=self.in_ptr[1:])
+        self.out_arc = np.argsort(self.src, kind="stable").astype(np.int32)
+        self.out_ptr = np.zeros(Q + 1, dtype=np.int32)
+        np.cumsum(np.bincount(self.src, minlength=Q), out=self.out_ptr[1:])
         self.cols = np.unique(self.label).astype(np.int32)
         self.col = np.searchsorted(self.cols, self.label).astype(np.int32)
         self.skipped = 0
         self._device: Dict[object, tuple] = {}
+        self._device_out: Dict[object, tuple] = {}
+
+    @classmethod
+    def from_arrays(cls, num_nodes: int, src, dst, label, w, final, outputs: Optional[Sequence] = None, large: bool = False) -> "DecodingGraph":
+        """DecodingGraph(num_nodes, zip(src, dst, label, w), final, outputs, large) from arrays, checked and built with numpy -
+        no Python loop over the arcs, so that a graph of millions of arcs builds in seconds.  final: one weight per node,
+        -inf for "not final"."""
+        Q = int(num_nodes)
+        max_nodes, max_arcs = cls._limits(large)
+        if not 1 <= Q <= max_nodes:
+            raise ValueError(f"DecodingGraph: {Q} nodes outside 1 .. {max_nodes}")
+        given = [np.asarray(x) for x in (src, dst, label, w)]
+        A = len(given[0])
+        if any(x.shape != (A,) for x in given):
+            raise ValueError(f"DecodingGraph.from_arrays: src, dst, label and w are one-dimensional and of one length, got {[x.shape for x in given]}")
+        if A > max_arcs:
+            raise ValueError(f"DecodingGraph: {A} arcs exceed {max_arcs}")
+        if any(x.dtype.kind not in "iu" for x in given[:3]):
+            raise ValueError("DecodingGraph.from_arrays: src, dst and label are integers")
+        src, dst, label = (x.astype(np.int64) for x in given[:3])
+        w64 = given[3].astype(np.float64)
+        if A and (min(src.min(), dst.min()) < 0 or max(src.max(), dst.max()) >= Q):
+            raise ValueError(f"DecodingGraph: an arc leaves the nodes 0 .. {Q - 1}")
+        if A and (label.min() < 1 or label.max() > np.iinfo(np.int32).max):
+            raise ValueError("DecodingGraph: a label is a token id >= 1 (0 is the blank; there are no epsilon arcs)")
+        if not np.isfinite(w64).all():
+            raise ValueError("DecodingGraph: a weight is finite")
+        fin = np.asarray(final, dtype=np.float32)
+        if fin.shape != (Q,):
+            raise ValueError(f"DecodingGraph: finals is one weight per node ({Q}), got {fin.shape}")
+        if np.isnan(fin).any() or np.isposinf(fin).any():
+            raise ValueError("DecodingGraph: a final weight is finite, or -inf for a node that is not final")
+        if outputs is not None and len(outputs) != A:
+            raise ValueError(f"DecodingGraph: one output per arc ({A}), got {len(outputs)}")
+        self = cls.__new__(cls)
+        self._tables(Q, src.astype(np.int32), dst.astype(np.int32), label.astype(np.int32), w64.astype(np.float32), fin, outputs, large)
+        return self
 
     # ---- builders ---------------------------------------------------------------------------------------------------
     @classmethod
@@ -85,11 +139,12 @@ class DecodingGraph:
 
     @classmethod
     def from_phrases(cls, phrases: Sequence[Sequence[int]], weights: Optional[Sequence[float]] = None,
-                     outputs: Optional[Sequence] = None, loop: bool = False) -> "DecodingGraph":
+                     outputs: Optional[Sequence] = None, loop: bool = False, large: bool = False) -> "DecodingGraph":
         """A prefix trie over the phrases (token-id sequences of at least one label, no two alike).  All but a phrase's last
         token share the trie's arcs; its last arc is its own - it carries weights[i] (default 0) and outputs[i] (default i)
         and ends in a final node of its own, so a phrase that is the beginning of another emits only its own output.
-        loop=True: the last arc returns to node 0, which is final, so sequences of phrases decode without epsilons."""
+        loop=True: the last arc returns to node 0, which is final, so sequences of phrases decode without epsilons (with
+        weights, a lexicon loop with a unigram weight per word).  large: as in the constructor."""
         phrases = [tuple(int(t) for t in p) for p in phrases]
         if not phrases or any(len(p) == 0 for p in phrases):
             raise ValueError("DecodingGraph.from_phrases: at least one phrase, each of at least one token")
@@ -118,14 +173,15 @@ class DecodingGraph:
             arcs.append((q, end, p[-1], wt))
             arc_out.append(out)
             finals[end] = 0.0
-        return cls(n, arcs, finals, arc_out)
+        return cls(n, arcs, finals, arc_out, large)
 
     @classmethod
-    def from_text(cls, lines: Iterable[str], token2id, weights: Optional[Sequence[float]] = None, loop: bool = False) -> "DecodingGraph":
+    def from_text(cls, lines: Iterable[str], token2id, weights: Optional[Sequence[float]] = None, loop: bool = False,
+                  large: bool = False) -> "DecodingGraph":
         """One phrase per line, split into the recipe's character tokens (every non-space character, as
         KeywordList.from_text); a phrase's output is its text.  A line with a character token2id does not list (or maps to the
         blank) is skipped and counted in `.skipped`; empty lines and repeated phrases (the first is kept) are dropped.
-        weights: one per line of `lines`."""
+        weights: one per line of `lines`.  large: as in the constructor."""
         phrases, texts, wts, seen, skipped = [], [], [], set(), 0
         for i, line in enumerate(lines):
             chars = [ch for ch in line if not ch.isspace()]
@@ -140,7 +196,7 @@ class DecodingGraph:
                 phrases.append(ids)
                 texts.append("".join(chars))
                 wts.append(0.0 if weights is None else float(weights[i]))
-        self = cls.from_phrases(phrases, wts, texts, loop)
+        self = cls.from_phrases(phrases, wts, texts, loop, large)
         self.skipped = skipped
         return self
 
@@ -206,19 +262,30 @@ class DecodingGraph:
         return (self.in_ptr.copy(), self.src.copy(), self.dst.copy(), self.label.copy(), self.col.copy(), self.w.copy(),
                 self.final.copy(), self.cols.copy())
 
-    def device_tables(self, device):
-        """host_tables() on `device`; made once per device and kept."""
+    def host_out_tables(self):
+        """The out-adjacency oe_beam_graph adds to host_tables(), as numpy: (out_ptr, out_arc)."""
+        return self.out_ptr.copy(), self.out_arc.copy()
+
+    def _on_device(self, cache, tables, device):
         import torch
         device = torch.device(device)
         if device.type != "cuda":
             raise TypeError(f"DecodingGraph: device tables live on a GPU (got {device})")
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        t = self._device.get(device)
+        t = cache.get(device)
         if t is None:
-            t = tuple(torch.from_numpy(a).to(device) for a in self.host_tables())
-            self._device[device] = t
+            t = tuple(torch.from_numpy(a).to(device) for a in tables())
+            cache[device] = t
         return t
+
+    def device_tables(self, device):
+        """host_tables() on `device`; made once per device and kept."""
+        return self._on_device(self._device, self.host_tables, device)
+
+    def device_out_tables(self, device):
+        """host_out_tables() on `device`; made once per device and kept."""
+        return self._on_device(self._device_out, self.host_out_tables, device)
 
     def accepts(self, frames: Sequence[int]) -> bool:
         """Does the graph accept the frame labelling `frames` (0 = blank) under the CTC topology?  A set simulation over the
