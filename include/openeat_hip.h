@@ -691,6 +691,78 @@ typedef struct oe_ctc_graph_beam_args {
 size_t oe_ctc_graph_beam_workspace_bytes(int B, int T, int U, int Q, int A, int max_active);
 int oe_ctc_graph_beam(const oe_ctc_graph_beam_args* args, void* stream);
 
+/* N-best grammar-constrained CTC decoding on device: the K best DISTINCT paths of the CTC posteriors through a token graph,
+ * each with the score of its best alignment - the first pass of a two-pass decode (WeNet takes the n-best of its TLG lattice
+ * and rescores them with the decoder).  These are the semantics every layer refers to.
+ *   oe_ctc_graph's, statement for statement: the graph struct oe_decoding_graph, the node states n[q] and arc states r[a], lp,
+ *   Tb = hlens[b] held to [0, T], normalized, the clamping of labels and indices, and float32 arithmetic.
+ *   A state holds an ordered list of at most K tokens, K = nbest, 1 <= K <= OE_CTC_GRAPH_NBEST_MAX, instead of one value.  A
+ *   token is (value, history); the history is the sequence of arcs traversed so far, the arc of an arc state included.  Before
+ *   frame 0, n[0] holds one token (0, the empty history); every other list is empty.
+ *   select_K of an ordered candidate list: sort stably by value, descending (among equal values the earlier candidate comes
+ *   first); walk the sorted list, skipping a candidate whose history equals that of a candidate already taken; stop after K.
+ *   An unreachable token (value -inf) is never a candidate.
+ *   For t = 0 .. Tb-1:
+ *     node q: the candidates are the tokens of n_{t-1}[q] in slot order, then, for every arc a' with dst[a'] == q by ascending
+ *       id, the tokens of r_{t-1}[a'] in slot order.  n_t[q] = select_K of them, with lp[t,0] added to every value.
+ *     arc a, s = src[a]: E = select_K of the tokens of n_{t-1}[s], then the tokens of r_{t-1}[a'] for every a' into s by
+ *       ascending id whose col differs from col[a] (the filter comes before the duplicate removal: a history that sits in a
+ *       same-label arc and in the node is still a candidate through the node).  The candidates of a are the stay tokens of
+ *       r_{t-1}[a] in slot order, then, for each E_k in order, (E_k.value + w[a], E_k.history followed by a).  r_t[a] =
+ *       select_K of them, with lp[t,label[a]] added to every value.  The weight is added after the selection of E, as
+ *       oe_ctc_graph adds it to the maximum.
+ *   End: the candidates are, for q ascending with final[q] > -inf, the tokens of n_{Tb-1}[q] with final[q] added, then, for a
+ *   ascending with final[dst[a]] > -inf, the tokens of r_{Tb-1}[a] with final[dst[a]] added; the hypotheses are select_K of
+ *   them.  Tb == 0 or no final state reachable: zero hypotheses.
+ *   distinct = OE_CTC_GRAPH_NBEST_ARCS (0): histories are arc sequences, the hypotheses are distinct paths.
+ *   distinct = OE_CTC_GRAPH_NBEST_TOKENS (1): a history is the sequence of the arcs' cols, the hypotheses are distinct token
+ *   sequences, each reporting the arcs of the best path that spells it (parallel arcs of one label and non-deterministic
+ *   branches collapse): the mode rescoring wants.
+ *   Two histories that differ at a state still differ after the same suffix, so the per-state lists lose nothing: up to float32
+ *   rounding the result is the K best distinct paths the graph accepts within Tb frames, each with the score of its best
+ *   alignment.  With nbest = 1 the arithmetic is oe_ctc_graph's own: hyp_score[:, 0] equals its score bit for bit and
+ *   hyp_arcs[:, 0] its traversal list, on continuous raw logits too.
+ *   History identity on the device is a 64-bit hash carried in the token: the empty history is 0, and appending id (the arc,
+ *   or its col) is h' = fin(h + 0x9E3779B97F4A7C15 * (id + 1)), fin the splitmix64 finaliser (full avalanche).  Two different
+ *   histories compare equal with probability about 2^-64 per comparison.  No output depends on a hash's value: ties are broken
+ *   by candidate order only.
+ *   Path recovery: every token carries the id of the record of its last "enter an arc" event; a record is the slot (t, a, k) of
+ *   a dense table of T*A*K int32 holding the parent record, the arc read off the id; after the end rule one thread per
+ *   hypothesis walks the chain.  Alignments of the hypotheses are not produced: oe_ctc_align, or oe_ctc_graph on the path's
+ *   linear chain, gives them.
+ *   out (device memory):
+ *        n_hyp (B) int32 = the number of hypotheses, 0 .. K;
+ *        hyp_score (B, K) float32, non-increasing, weights and final weight included, -inf in unused slots;
+ *        hyp_len (B, K) int32 = the number of arcs of the path, which may exceed max_len; -1 in unused slots.  The empty path
+ *        (the start node final, every frame blank) is a hypothesis of length 0;
+ *        hyp_arcs / hyp_tokens (B, K, max_len) int32 = the first max_len arcs and their labels (label[a] as given), -1 behind.
+ *   Limits: 1 <= B, 1 <= T <= 2^20, V > 1, ldv >= V, 1 <= U < V, 1 <= Q <= OE_CTC_GRAPH_MAX_NODES, 1 <= A <=
+ *   OE_CTC_GRAPH_MAX_ARCS (any graph the dense search takes), 1 <= nbest <= 8, max_len >= 1, distinct in {0, 1}, T*A*K < 2^31.
+ *   Anything else, and any NULL required pointer (logits, hlens, graph and its eight tables, the five outputs, workspace), is
+ *   reported through oe_last_error before any launch, with the outputs untouched.
+ *   workspace: oe_ctc_graph_nbest_workspace_bytes(B,T,U,Q,A,nbest) bytes, 16-byte aligned (0 for shapes outside the limits).
+ *   Tokens are 16 bytes (value, record, hash).  Per utterance: the double-buffered token lists of the arcs and the nodes,
+ *   16*K*(2*A + 2*Q); the per-node lists "without the arcs of label c" for at most K labels c, 16*K*K*Q, and their labels,
+ *   4*K*Q; the record table, 4*T*A*K; the lp rows of oe_ctc_kws, 4*T*(U+1):
+ *     16*B*K*(2*A + 2*Q + K*Q) + 4*B*(K*Q + T*A*K + T*(U+1)), rounded up to 16.
+ *   It is the record table that callers feel.  Utterances are independent, so a caller short of memory runs them in groups.
+ * Two launches (the row pass of oe_ctc_kws; one workgroup per utterance - 1024 threads, 512 where nbest > 2 - with the token
+ * lists in the workspace, where they stay in L2).  No workgroup waits for another, no float atomics; no allocation, no host read, no host-side state:
+ * capturable.  Every output is bit-identical from run to run and depends on its own utterance only. */
+#define OE_CTC_GRAPH_NBEST_MAX 8
+#define OE_CTC_GRAPH_NBEST_ARCS 0
+#define OE_CTC_GRAPH_NBEST_TOKENS 1
+typedef struct oe_ctc_graph_nbest_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_decoding_graph* graph;
+    int normalized, nbest, distinct, max_len;
+    int* n_hyp; float* hyp_score; int* hyp_len; int* hyp_arcs; int* hyp_tokens;
+    void* workspace;
+} oe_ctc_graph_nbest_args;
+size_t oe_ctc_graph_nbest_workspace_bytes(int B, int T, int U, int Q, int A, int nbest);
+int oe_ctc_graph_nbest(const oe_ctc_graph_nbest_args* args, void* stream);
+
 /* Graph CTC likelihood on device: the sum half of oe_ctc_graph.  logZ = log of the sum, over every path the graph accepts and
  * every CTC alignment of it, of the path's probability times exp(its weights), and its gradient with respect to raw logits
  * (what k2 / WeNet users know as a graph CTC loss; the reference has none).  With normalised posteriors and zero weights

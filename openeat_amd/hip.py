@@ -245,6 +245,19 @@ class CtcGraphArgs(C.Structure):
                 ("workspace", c_fp)]
 
 
+class CtcGraphNbestArgs(C.Structure):
+    """oe_ctc_graph_nbest_args (include/openeat_hip.h); filled by ops.ctc_graph_nbest.  A struct assigned through C.pointer to
+    graph stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("graph", C.POINTER(DecodingGraph)), ("normalized", C.c_int), ("nbest", C.c_int),
+                ("distinct", C.c_int), ("max_len", C.c_int),
+                ("n_hyp", c_fp), ("hyp_score", c_fp), ("hyp_len", c_fp), ("hyp_arcs", c_fp), ("hyp_tokens", c_fp),
+                ("workspace", c_fp)]
+
+
+CTC_GRAPH_NBEST_MAX = 8                                         # OE_CTC_GRAPH_NBEST_MAX
+CTC_GRAPH_NBEST_ARCS, CTC_GRAPH_NBEST_TOKENS = 0, 1            # OE_CTC_GRAPH_NBEST_*: what makes two hypotheses distinct
+
 CTC_GRAPH_BEAM_OK, CTC_GRAPH_BEAM_INFEASIBLE, CTC_GRAPH_BEAM_OVERFLOW = 0, 1, 2      # OE_CTC_GRAPH_BEAM_*: oe_ctc_graph_beam's status
 
 
@@ -339,6 +352,8 @@ _SIGNATURES = {
     "oe_ctc_kws": (I, [C.POINTER(CtcKwsArgs), P]),
     "oe_ctc_graph_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph": (I, [C.POINTER(CtcGraphArgs), P]),
+    "oe_ctc_graph_nbest_workspace_bytes": (SZ, [I, I, I, I, I, I]),
+    "oe_ctc_graph_nbest": (I, [C.POINTER(CtcGraphNbestArgs), P]),
     "oe_ctc_graph_beam_workspace_bytes": (SZ, [I, I, I, I, I, I]),
     "oe_ctc_graph_beam": (I, [C.POINTER(CtcGraphBeamArgs), P]),
     "oe_ctc_graph_logp_workspace_bytes": (SZ, [I, I, I, I, I]),

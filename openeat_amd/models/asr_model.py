@@ -502,7 +502,8 @@ class ASRModel(torch.nn.Module):
     @torch.no_grad()
     def ctc_graph_search(self, features: torch.Tensor, features_length: torch.Tensor, graph, window: Optional[int] = None,
                          margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10, posterior: bool = False,
-                         beam: Optional[float] = None, max_active: Optional[int] = None, workspace_cap: int = 1 << 30):
+                         beam: Optional[float] = None, max_active: Optional[int] = None, workspace_cap: int = 1 << 30,
+                         nbest: Optional[int] = None, distinct: str = "arcs"):
         """Grammar-constrained CTC decoding (the reference has none; semantics in include/openeat_hip.h, oe_ctc_graph): the
         best path of each utterance through `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph - the output is in the
         grammar by construction, or the utterance is infeasible.  Logits by ctc_logits_windowed (window None: one plain pass),
@@ -516,7 +517,10 @@ class ASRModel(torch.nn.Module):
         states below the frame's best - beam are dropped, and max_active (default 16384) is how many survivors a frame can
         record.  An utterance that overflows is run again, alone with the others that did, with max_active doubled (and at
         least its peak), for as long as one utterance's workspace stays within workspace_cap; after that a RuntimeError names the
-        utterance and its peak.  An utterance may be infeasible through pruning alone; a wider beam is the remedy."""
+        utterance and its peak.  An utterance may be infeasible through pruning alone; a wider beam is the remedy.
+        nbest = K (1 .. 8; dense search only, a ValueError with beam): every result also carries .nbest, the K best distinct
+        paths (distinct="arcs") or token sequences (distinct="tokens") as GraphHypothesis, best first (ops.ctc_graph_nbest,
+        semantics at oe_ctc_graph_nbest): one more pass on the device and one more D2H copy.  nbest[0] is the 1-best's path."""
         from openeat_amd.utils.decoding_graph import LOGP_MAX_ARCS, LOGP_MAX_NODES, DecodingGraph, graph_results
         if not isinstance(graph, DecodingGraph):
             raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
@@ -525,6 +529,8 @@ class ASRModel(torch.nn.Module):
                              f"nodes and {LOGP_MAX_ARCS} arcs; this graph has {graph.num_nodes} / {graph.num_arcs}")
         if beam is None and max_active is not None:
             raise ValueError("max_active belongs to the beam search: give a beam (inf for none) with it")
+        if nbest is not None and beam is not None:
+            raise ValueError("nbest belongs to the dense search: n-best over the token-passing search (beam) is not built")
         assert features.shape[0] == features_length.shape[0]
         logits, lens = self.ctc_logits_windowed(features, features_length, window, margin)
         if beam is None:
@@ -545,7 +551,60 @@ class ASRModel(torch.nn.Module):
             for res, m, best in zip(results, mass, score.cpu().tolist()):
                 if res.feasible:
                     res.log_mass, res.posterior = m, min(math.exp(best - m), 1.0)
+        if nbest is not None:
+            for res, hyps in zip(results, self._graph_nbest_host(logits, lens, graph, int(nbest), distinct, int(workspace_cap))[0]):
+                res.nbest = hyps
         return results
+
+    @staticmethod
+    def _graph_nbest_host(logits, lens, graph, nbest, distinct, workspace_cap=1 << 30):
+        """ops.ctc_graph_nbest and ONE D2H copy of its results -> (per utterance its GraphHypothesis list, the device tensors)."""
+        from openeat_amd.utils.decoding_graph import graph_hypotheses
+        outs = ops.ctc_graph_nbest(logits, lens, graph, nbest, distinct, workspace_cap=workspace_cap)
+        n_hyp, hyp_score, hyp_len, hyp_arcs, hyp_tokens = outs
+        B, K, M = hyp_arcs.shape
+        packed = torch.cat([n_hyp.double(), hyp_score.double().flatten(), hyp_len.double().flatten(), hyp_arcs.double().flatten(),
+                            hyp_tokens.double().flatten()]).cpu()
+        n, sc, ln, (ar, tk) = packed[:B], packed[B: B + B * K], packed[B + B * K: B + 2 * B * K], packed[B + 2 * B * K:].split(B * K * M)
+        as_int = lambda t, *shape: t.long().view(*shape).tolist()
+        return graph_hypotheses(graph, as_int(n, B), sc.view(B, K).tolist(), as_int(ln, B, K), as_int(ar, B, K, M), as_int(tk, B, K, M)), outs
+
+    @torch.no_grad()
+    def graph_attention_rescoring(self, features: torch.Tensor, features_length: torch.Tensor, graph, nbest: int = 4,
+                                  ctc_weight: float = 0.0, reverse_weight: float = 0.0, lm: Optional[torch.nn.Module] = None,
+                                  lm_weight: float = 0.0):
+        """The two-pass decode with a grammar as the first pass (WeNet rescores the n-best of its TLG lattice; the reference's
+        attention_rescoring takes its n-best from the prefix beam search): ONE encoder pass, the `nbest` best distinct token
+        sequences of `graph` on the CTC logits (ops.ctc_graph_nbest, distinct="tokens"; semantics at oe_ctc_graph_nbest), then
+        the bi-decoder pass and the score mix of attention_rescoring_batch (asr_model.py:504-528) over all B x nbest
+        hypotheses, their graph scores as the CTC scores.  Returns per utterance the picked GraphHypothesis - score the mixed
+        score, rank its place in the first pass; for an utterance the graph cannot accept, an infeasible GraphHypothesis (score -inf,
+        rank -1, feasible False)."""
+        from openeat_amd.utils.decoding_graph import DecodingGraph, GraphHypothesis
+        if not isinstance(graph, DecodingGraph):
+            raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+        if reverse_weight > 0 and self.decoder.r_num_blocks == 0:
+            raise IndexError("reverse_weight > 0 needs r_decoder_num_blocks > 0 (as in the reference)")
+        assert features.shape[0] == features_length.shape[0]
+        nbest = int(nbest)
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        lens = encoder_mask.squeeze(1).sum(1)
+        hyps, (n_hyp, hyp_score, hyp_len, _, hyp_tokens) = self._graph_nbest_host(self.ctc.logits(encoder_out), lens, graph, nbest, "tokens")
+        B, K, M = hyp_tokens.shape
+        Lm = max(max((len(h.tokens) for hs in hyps for h in hs), default=0), 1)
+        _, _, _, best, mixed = self._rescore_stage2(encoder_out, encoder_mask, hyp_tokens.view(B * K, M), hyp_len.view(B * K),
+                                                    hyp_score.view(B * K).double(), Lm, K, ctc_weight, reverse_weight, lm, lm_weight,
+                                                    with_scores=True)
+        best, mixed = best.cpu().tolist(), mixed.cpu().tolist()
+        picks = []
+        for b in range(B):
+            if not hyps[b]:
+                picks.append(GraphHypothesis(rank=-1))
+                continue
+            h = hyps[b][best[b]]
+            h.score = float(mixed[b][best[b]])
+            picks.append(h)
+        return picks
 
     @staticmethod
     def _graph_beam_decode(logits, lens, graph, beam, max_active, workspace_cap):
@@ -871,9 +930,10 @@ class ASRModel(torch.nn.Module):
                 None if r.bias is None else r.bias.view(R))
 
     def _rescore_stage2(self, encoder_out, encoder_mask, pre, plen, ctc_scores, Lm, beam_size, ctc_weight, reverse_weight, lm, lm_weight,
-                        bias=None):
+                        bias=None, with_scores=False):
         """The n-best lists as device tensors -> (tokens (B, Lm) of the rescored pick, their lengths (B), mean n-best length).
-        Lm >= the longest hypothesis (any padding is ignore_id and masked).  bias (R) float64: added to the mixed scores."""
+        Lm >= the longest hypothesis (any padding is ignore_id and masked).  bias (R) float64: added to the mixed scores.
+        with_scores: also the pick's slot (B) and the mixed scores (B, beam) float64 it is the arg-max of."""
         device = pre.device
         B = encoder_out.shape[0]
         missing = plen < 0
@@ -881,6 +941,12 @@ class ASRModel(torch.nn.Module):
         ori = pre[:, :Lm].long()
         ori = ori.masked_fill(torch.arange(Lm, device=device).unsqueeze(0) >= hl.unsqueeze(1), self.ignore_id)
         ctc_scores = ctc_scores.masked_fill(missing, -float("inf"))
+        if with_scores:
+            mixed = self._rescore_mix(encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight,
+                                      lm, lm_weight, bias)
+            best = mixed.argmax(1)
+            pick = best + torch.arange(B, device=device) * beam_size
+            return ori.index_select(0, pick), hl.index_select(0, pick), hl.float().mean(), best, mixed
         best = self._rescore_scores(encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight,
                                     lm, lm_weight, bias)
         pick = best + torch.arange(B, device=device) * beam_size
@@ -890,6 +956,12 @@ class ASRModel(torch.nn.Module):
                         lm_weight, bias=None):
         """asr_model.py:504-528 for all B x beam hypotheses at once: index of the best hypothesis per utterance.
         bias (R) float64 or None: the hypotheses' hotword scores, added to the mix."""
+        return self._rescore_mix(encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight, lm,
+                                 lm_weight, bias).argmax(1)
+
+    def _rescore_mix(self, encoder_out, encoder_mask, ori, hl, ctc_scores, missing, Lm, beam_size, ctc_weight, reverse_weight, lm,
+                     lm_weight, bias=None):
+        """_rescore_scores before the arg-max: the mixed scores (B, beam) float64, -inf for a missing slot."""
         device = ori.device
         B = encoder_out.shape[0]
         R = B * beam_size
@@ -926,7 +998,7 @@ class ASRModel(torch.nn.Module):
         if bias is not None:
             score = score + bias
         score = score.masked_fill(missing, -float("inf"))         # (0 * -inf above would be nan: the slot is out whatever the weights)
-        return score.view(B, beam_size).argmax(1)
+        return score.view(B, beam_size)
 
     def _rescoring_batch_graphs(self, features, features_length, spec, ctc_weight, reverse_weight, lm, lm_weight):
         """The same two stages replayed from HIP graphs (decode is launch-bound: ~1500 small launches for 64 utterances):

@@ -2496,6 +2496,60 @@ def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, work
     return outs
 
 
+def ctc_graph_nbest(logits, hlens, graph, nbest, distinct="arcs", normalized=False, max_len=None, workspace_cap=1 << 30):
+    """N-best grammar-constrained CTC decoding (oe_ctc_graph_nbest; semantics in include/openeat_hip.h): logits (B, T, V)
+    float32 (raw, or log-probabilities with normalized=True), hlens (B), graph an
+    openeat_amd.utils.decoding_graph.DecodingGraph, 1 <= nbest <= 8, distinct "arcs" (distinct paths) or "tokens" (distinct
+    token sequences, each with its best path) -> device tensors (n_hyp (B) int32, hyp_score (B, nbest) float32, hyp_len
+    (B, nbest) int32, hyp_arcs, hyp_tokens (B, nbest, max_len) int32).  max_len None: T, which no path exceeds.  The workspace
+    is dominated by the record table, 4 * T * A * nbest bytes per utterance; where the batch exceeds workspace_cap the
+    utterances - they are independent - run in consecutive groups of as many as fit, one workspace reused: exactly the results
+    of one call.  One utterance alone above the cap is a ValueError that names the bytes."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph
+    if not isinstance(graph, DecodingGraph):
+        raise TypeError(f"ctc_graph_nbest: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    modes = {"arcs": hip.CTC_GRAPH_NBEST_ARCS, "tokens": hip.CTC_GRAPH_NBEST_TOKENS}
+    if distinct not in modes:
+        raise ValueError(f"ctc_graph_nbest: distinct is 'arcs' or 'tokens', got {distinct!r}")
+    logits = _chk(logits, "ctc_graph_nbest")
+    if logits.dim() != 3:
+        raise ValueError(f"ctc_graph_nbest: logits must be (B, T, V), got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    B, T, V = logits.shape
+    dev = logits.device
+    nbest = int(nbest)
+    max_len = T if max_len is None else int(max_len)
+    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
+    lib = hip.lib()
+    per_utt = lib.oe_ctc_graph_nbest_workspace_bytes(1, T, U, Q, A, nbest) if B >= 1 else 0
+    if per_utt == 0 or max_len < 1 or U >= V:
+        raise ValueError(f"ctc_graph_nbest: B={B} T={T} nbest={nbest} max_len={max_len} U={U} V={V} Q={Q} A={A} outside 1 <= B, "
+                         "1 <= T <= 2^20, 1 <= nbest <= 8, 1 <= max_len, 1 <= U < V, 1 <= Q <= 8064, 1 <= A <= 16384, T*A*nbest < 2^31")
+    if per_utt > int(workspace_cap):
+        raise ValueError(f"ctc_graph_nbest: one utterance needs a workspace of {per_utt} bytes (T={T} A={A} nbest={nbest}: the record "
+                         f"table alone is {4 * T * A * nbest}), above workspace_cap={int(workspace_cap)}")
+    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
+    hyp_score = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    hyp_len = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    hyp_arcs = torch.empty(B, nbest, max_len, dtype=torch.int32, device=dev)
+    hyp_tokens = torch.empty(B, nbest, max_len, dtype=torch.int32, device=dev)
+    outs = (n_hyp, hyp_score, hyp_len, hyp_arcs, hyp_tokens)
+    group = min(int(workspace_cap) // per_utt, B)
+    ws = torch.empty(lib.oe_ctc_graph_nbest_workspace_bytes(group, T, U, Q, A, nbest), dtype=torch.uint8, device=dev)
+    g = hip.decoding_graph(graph, dev)
+    for lo in range(0, B, group):
+        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
+        a = hip.CtcGraphNbestArgs()
+        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
+        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+        a.normalized, a.nbest, a.distinct, a.max_len = int(bool(normalized)), nbest, modes[distinct], max_len
+        a.n_hyp, a.hyp_score, a.hyp_len, a.hyp_arcs, a.hyp_tokens = (t[lo:].data_ptr() for t in outs)
+        a.workspace = ws.data_ptr()
+        hip.check(lib.oe_ctc_graph_nbest(hip.C.byref(a), hip.stream()), "oe_ctc_graph_nbest")
+    return outs
+
+
 def ctc_graph_beam_decode(logits, hlens, graph, beam, max_active=16384, normalized=False, max_trav=None, workspace_cap=1 << 30):
     """Beam-pruned CTC decoding over a large token graph (oe_ctc_graph_beam; semantics in include/openeat_hip.h): logits
     (B, T, V) float32 (raw, or log-probabilities with normalized=True), hlens (B), graph an

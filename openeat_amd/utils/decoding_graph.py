@@ -1,5 +1,5 @@
-"""Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode, ops.ctc_graph_beam_decode;
-semantics in include/openeat_hip.h, oe_ctc_graph and oe_ctc_graph_beam): the token graph with the tables the kernels read, its
+"""Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode, ops.ctc_graph_beam_decode,
+ops.ctc_graph_nbest; semantics in include/openeat_hip.h, oe_ctc_graph, oe_ctc_graph_beam and oe_ctc_graph_nbest): the token graph with the tables the kernels read, its
 builders, and the records made of the kernels' outputs; and GraphSet, the packed form oe_ctc_graph_logp reads.  No kernel here."""
 import math
 from dataclasses import dataclass, field
@@ -411,7 +411,8 @@ class GraphResult:
     it - and with times "start_s" / "end_s";  score: the path's value, weights and final weight included (-inf if infeasible);
     truncated: more traversals than were asked for, only the first are listed;  log_mass, posterior (ctc_graph_search with
     posterior=True, else None): the graph's total log-likelihood on the normalised posteriors (oe_ctc_graph_logp) - with zero
-    weights log P(the labelling is in the grammar) - and exp(score - log_mass), the best path's share of it."""
+    weights log P(the labelling is in the grammar) - and exp(score - log_mass), the best path's share of it;  nbest
+    (ctc_graph_search with nbest=K, else None): the K best distinct paths as GraphHypothesis, best first."""
     feasible: bool
     score: float
     tokens: List[int] = field(default_factory=list)
@@ -420,6 +421,7 @@ class GraphResult:
     truncated: bool = False
     log_mass: Optional[float] = None
     posterior: Optional[float] = None
+    nbest: Optional[List["GraphHypothesis"]] = None
 
     @property
     def confidences(self) -> List[float]:
@@ -457,4 +459,38 @@ def graph_results(graph: DecodingGraph, score, n_trav, trav_arc, trav_start, tra
                 res.outputs.append(out)
                 first, logp, frames = None, 0.0, 0
         results.append(res)
+    return results
+
+
+@dataclass
+class GraphHypothesis:
+    """One of the n best paths of an utterance through a DecodingGraph (oe_ctc_graph_nbest).  tokens: a label per arc of the
+    path;  arcs: the arc ids;  outputs: the outputs of the arcs that carry one, in path order;  score: the value of the path's
+    best alignment, weights and final weight included (after graph_attention_rescoring: the mixed score);  rank: the position
+    in the first pass's list, 0 the best (-1 with score -inf: the infeasible result of graph_attention_rescoring);  truncated: the path has more arcs than were asked for, only the first are listed."""
+    tokens: List[int] = field(default_factory=list)
+    arcs: List[int] = field(default_factory=list)
+    outputs: List = field(default_factory=list)
+    score: float = NEG_INF
+    rank: int = 0
+    truncated: bool = False
+
+    @property
+    def feasible(self) -> bool:
+        return self.score > NEG_INF
+
+
+def graph_hypotheses(graph: DecodingGraph, n_hyp, hyp_score, hyp_len, hyp_arcs, hyp_tokens) -> List[List[GraphHypothesis]]:
+    """The outputs of ops.ctc_graph_nbest, already on the host as nested lists (n_hyp (B); hyp_score, hyp_len (B, K); hyp_arcs,
+    hyp_tokens (B, K, max_len)) -> per utterance the list of its GraphHypothesis, best first (empty if infeasible)."""
+    results = []
+    for b, n in enumerate(n_hyp):
+        hyps = []
+        for k in range(int(n)):
+            stored = len(hyp_arcs[b][k])
+            m = min(int(hyp_len[b][k]), stored)
+            arcs = [int(a) for a in hyp_arcs[b][k][:m]]
+            hyps.append(GraphHypothesis([int(t) for t in hyp_tokens[b][k][:m]], arcs, [graph.outputs[a] for a in arcs if graph.outputs[a] is not None],
+                                        float(hyp_score[b][k]), k, int(hyp_len[b][k]) > stored))
+        results.append(hyps)
     return results
