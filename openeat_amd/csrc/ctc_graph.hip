@@ -3,8 +3,7 @@
 // (oe_ctc_graph); the tie rule is oe_ctc_align's, generalised.
 //
 // Per utterance there is a value per node (n: last frame blank) and per arc (r: last frame emitted the arc's label).  Two launches:
-//   launch 1  graph_rows_kernel: kws_rows_kernel's row pass (one wave per frame; the row read once, its log-sum-exp taken, the
-//             blank and the U label columns kept as lp in a compact row of U + 1 floats).
+//   launch 1  lp_rows_kernel (lp_rows.hip): the blank and the U label columns of every frame as lp, a compact row of U + 1 floats.
 //   launch 2  graph_kernel: ONE WORKGROUP of 1024 threads PER UTTERANCE, the state values in LDS.  A frame is two phases
 //             with a barrier behind each:
 //             A  per node q, over its incoming arcs (they are contiguous: arcs are sorted by dst): the best r, lowest id on
@@ -28,13 +27,12 @@
 //             loaded during frame t (GRAPH_PF = 1); the arcs behind it read theirs from L2 inside phase B.
 // No workgroup waits for another, no float atomics, no allocation, no host read: capturable.
 #include <stdlib.h>
-#include "oe_common.h"
+#include "ctc_graph_common.h"
 #include "../../include/openeat_hip.h"
 
 #define GRAPH_BLOCK 1024
 #define GRAPH_WAVES (GRAPH_BLOCK / 64)
 #define GRAPH_PF 1                                // frames of lp in flight ahead of the recursion (a thread's first arc)
-#define GRAPH_MAX_T (1 << 20)
 #define GRAPH_MAX_A OE_CTC_GRAPH_MAX_ARCS
 #define GRAPH_MAX_Q OE_CTC_GRAPH_MAX_NODES
 #define GRAPH_HEAVY 32                            // a node of more incoming arcs than this takes a wave, not a thread
@@ -43,48 +41,6 @@
 
 static_assert(4 * GRAPH_MAX_A + 12 * GRAPH_MAX_Q + 2 * GRAPH_MAX_HEAVY + 512 <= 160 * 1024, "oe_ctc_graph: the limits exceed the LDS");
 static_assert(GRAPH_MAX_A <= 0x7fff, "oe_ctc_graph: an arc id and 'none' must fit 15 bits of a back-pointer word");
-
-// ---------------------------------------------------------------- launch 1 ----
-// kws_rows_kernel (ctc_kws.hip), statement for statement.
-__global__ __launch_bounds__(256) void graph_rows_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                          const int* __restrict__ hlens, const int* __restrict__ cols, int U,
-                                                          int normalized, float* __restrict__ cw) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    float c = 0.f;
-    if (!normalized) {
-        float m = -INFINITY, s = 0.f;
-        int i = lane;
-        for (; i + 7 * 64 < V; i += 8 * 64) {
-            float x[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = p[i + k * 64];
-            float mx = x[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) mx = fmaxf(mx, x[k]);
-            if (mx > m) { s *= expf(m - mx); m = mx; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += expf(x[k] - m);
-        }
-        for (; i < V; i += 64) {
-            const float x = p[i];
-            if (x > m) { s *= expf(m - x); m = x; }
-            s += expf(x - m);
-        }
-        const float wm = wave_max(m);
-        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - wm));
-        c = wm + logf(s);
-    }
-    float* out = cw + row * (long)(U + 1);
-    for (int u = lane; u <= U; u += 64) {
-        const int col = u == 0 ? 0 : min(max(cols[u - 1], 0), V - 1);       // a label outside [0, V) must not become a wild read
-        out[u] = p[col] - c;
-    }
-}
 
 // ---------------------------------------------------------------- launch 2 ----
 struct GraphParams {
@@ -99,8 +55,6 @@ struct GraphParams {
 // The two best of a set of incoming arcs: (v1, id1, c1) the best, lowest id on ties, and its label; (v2, id2) the best among
 // the arcs whose label is not c1.  An unreachable arc (-inf) never enters: "none" is (-inf, GRAPH_NONE, -1).
 struct TwoBest { float v1; int id1, c1; float v2; int id2; };
-
-__device__ __forceinline__ bool graph_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
 // arcs arrive by ascending id: strictly greater replaces
 __device__ __forceinline__ void graph_push(TwoBest& s, float v, int id, int c) {
@@ -368,22 +322,14 @@ extern "C" size_t oe_ctc_graph_workspace_bytes(int B, int T, int U, int Q, int A
 extern "C" int oe_ctc_graph(const oe_ctc_graph_args* args, void* stream) {
     OE_REQUIRE(args, "oe_ctc_graph: null args");
     const oe_ctc_graph_args& a = *args;
-    OE_REQUIRE(a.graph, "oe_ctc_graph: null graph");
+    if (int rc = graph_check("oe_ctc_graph", a.graph, a.logits, a.ldv, a.B, a.T, a.V, a.hlens, a.workspace, &a.max_trav)) return rc;
     const oe_decoding_graph& g = *a.graph;
-    OE_REQUIRE(a.logits, "oe_ctc_graph: null logits");
-    OE_REQUIRE(a.hlens, "oe_ctc_graph: null hlens");
     OE_REQUIRE(a.score && a.frames && a.arcs && a.n_trav && a.trav_arc && a.trav_start && a.trav_end,
                "oe_ctc_graph: null output (score, frames, arcs, n_trav, trav_arc, trav_start, trav_end)");
-    OE_REQUIRE(a.workspace, "oe_ctc_graph: null workspace");
-    OE_REQUIRE(a.B > 0 && a.T > 0 && a.T <= GRAPH_MAX_T && a.V > 1 && a.ldv >= a.V,
-               "oe_ctc_graph: bad shape B=%d T=%d V=%d ldv=%ld (1 <= B, 1 <= T <= 2^20, ldv >= V)", a.B, a.T, a.V, a.ldv);
     OE_REQUIRE(g.Q >= 1 && g.Q <= GRAPH_MAX_Q, "oe_ctc_graph: Q=%d nodes outside 1 .. %d (the node values live in LDS)", g.Q, GRAPH_MAX_Q);
     OE_REQUIRE(g.A >= 1 && g.A <= GRAPH_MAX_A, "oe_ctc_graph: A=%d arcs outside 1 .. %d (the arc values live in LDS)", g.A, GRAPH_MAX_A);
-    OE_REQUIRE(g.U >= 1 && g.U < a.V, "oe_ctc_graph: U=%d distinct labels outside 1 .. V-1 = %d", g.U, a.V - 1);
     OE_REQUIRE(g.in_ptr && g.src && g.dst && g.label && g.col && g.w && g.final && g.cols,
                "oe_ctc_graph: null table in graph (in_ptr, src, dst, label, col, w, final, cols)");
-    OE_REQUIRE(a.max_trav >= 1, "oe_ctc_graph: max_trav=%d < 1", a.max_trav);
-    OE_REQUIRE((((uintptr_t)a.workspace) & 15) == 0, "oe_ctc_graph: workspace must be 16-byte aligned");
     const size_t lds_max = 4 * (size_t)GRAPH_MAX_A + 12 * (size_t)GRAPH_MAX_Q;
     const bool cols_in_lds = 8 * (size_t)g.A + 12 * (size_t)g.Q <= lds_max;
     const size_t lds = (cols_in_lds ? 8 : 4) * (size_t)g.A + 12 * (size_t)g.Q;
@@ -401,9 +347,8 @@ extern "C" int oe_ctc_graph(const oe_ctc_graph_args* args, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     float* cw = reinterpret_cast<float*>(a.workspace);
     const long rows = (long)a.B * a.T;
-    hipLaunchKernelGGL(graph_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, g.cols, g.U,
-                       a.normalized, cw);
-    OE_LAUNCH_CHECK("ctc_graph_rows");
+    if (int rc = oe_lp_rows("oe_ctc_graph", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, g.cols, g.U, a.normalized, cw, nullptr, st))
+        return rc;
     GraphParams p;
     p.cw = cw;
     p.bp = reinterpret_cast<unsigned*>(cw + rows * ((long)g.U + 1));

@@ -2,7 +2,7 @@
 // to are in include/openeat_hip.h (oe_ctc_graph_beam); the arithmetic, the tie rule and the end rule are ctc_graph.hip's.
 //
 // Two launches:
-//   launch 1  beam_rows_kernel: kws_rows_kernel's row pass (ctc_kws.hip), statement for statement.
+//   launch 1  lp_rows_kernel (lp_rows.hip): the blank and the U label columns of every frame as lp, a compact row of U + 1 floats.
 //   launch 2  beam_kernel: ONE WORKGROUP of 1024 threads PER UTTERANCE, the state in global memory.
 // Per utterance, dense and paid once (the stamps and keys are zeroed before frame 0, everything else is guarded by a stamp):
 //   per arc   rv value, rs stamp, rpos position in the list it is alive in;
@@ -30,60 +30,18 @@
 // Values written by an atomic (keys, tstamp) are read by atomic loads; everything else is written and read by the waves of
 // one workgroup with a barrier between.  No workgroup waits for another, no float atomics, no allocation, no host read.
 #include <stdlib.h>
-#include "oe_common.h"
+#include "ctc_graph_common.h"
 #include "../../include/openeat_hip.h"
 
 #define BEAM_BLOCK 1024
 #define BEAM_WAVES (BEAM_BLOCK / 64)
-#define BEAM_MAX_T (1 << 20)
+#define BEAM_MAX_T GRAPH_MAX_T
 #define BEAM_MAX_Q OE_CTC_GRAPH_BEAM_MAX_NODES
 #define BEAM_MAX_A OE_CTC_GRAPH_BEAM_MAX_ARCS
 #define BEAM_WIDE 16                              // a node of more leaving arcs than this takes a wave, not a thread
 #define BEAM_NONE 0x7fffffff
 
 typedef unsigned long long beam_u64;
-
-// ---------------------------------------------------------------- launch 1 ----
-// kws_rows_kernel (ctc_kws.hip), statement for statement.
-__global__ __launch_bounds__(256) void beam_rows_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                         const int* __restrict__ hlens, const int* __restrict__ cols, int U,
-                                                         int normalized, float* __restrict__ cw) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    float c = 0.f;
-    if (!normalized) {
-        float m = -INFINITY, s = 0.f;
-        int i = lane;
-        for (; i + 7 * 64 < V; i += 8 * 64) {
-            float x[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = p[i + k * 64];
-            float mx = x[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) mx = fmaxf(mx, x[k]);
-            if (mx > m) { s *= expf(m - mx); m = mx; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += expf(x[k] - m);
-        }
-        for (; i < V; i += 64) {
-            const float x = p[i];
-            if (x > m) { s *= expf(m - x); m = x; }
-            s += expf(x - m);
-        }
-        const float wm = wave_max(m);
-        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - wm));
-        c = wm + logf(s);
-    }
-    float* out = cw + row * (long)(U + 1);
-    for (int u = lane; u <= U; u += 64) {
-        const int col = u == 0 ? 0 : min(max(cols[u - 1], 0), V - 1);       // a label outside [0, V) must not become a wild read
-        out[u] = p[col] - c;
-    }
-}
 
 // ---------------------------------------------------------------- launch 2 ----
 // The per-utterance workspace: byte offsets of its parts, every one a multiple of 16 (Q, A, M are rounded up to 4).
@@ -140,7 +98,6 @@ __device__ __forceinline__ beam_u64 beam_key(float v, int id) {
 __device__ __forceinline__ int beam_key_id(beam_u64 k) { return (int)~(unsigned)k; }
 __device__ __forceinline__ beam_u64 beam_load(const beam_u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void beam_clear(beam_u64* p) { __hip_atomic_store(p, (beam_u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ bool beam_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
 // A slot in a list for every lane that wants one, one add per wave.  Called by whole waves only (uniform control flow).
 __device__ __forceinline__ int beam_append(int* counter, bool want) {
@@ -418,21 +375,21 @@ __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const BeamParams p) {
         for (int i = tid; i < n; i += BEAM_BLOCK) {
             const int c = L[i].x;
             const float v = c < Q ? nv[c] + p.fin[c] : rv[c - Q] + p.fin[dst_of(c - Q)];
-            if (beam_better(v, c, bv, bi)) { bv = v; bi = c; bp = i; }
+            if (graph_better(v, c, bv, bi)) { bv = v; bi = c; bp = i; }
         }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float v = __shfl_xor(bv, o, 64);
         const int i = __shfl_xor(bi, o, 64), q = __shfl_xor(bp, o, 64);
-        if (beam_better(v, i, bv, bi)) { bv = v; bi = i; bp = q; }
+        if (graph_better(v, i, bv, bi)) { bv = v; bi = i; bp = q; }
     }
     __syncthreads();                                                          // red_v was read in the last frame
     if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; red_p[wave] = bp; }
     __syncthreads();
     if (tid == 0) {
         for (int i = 1; i < BEAM_WAVES; ++i)
-            if (beam_better(red_v[i], red_i[i], bv, bi)) { bv = red_v[i]; bi = red_i[i]; bp = red_p[i]; }
+            if (graph_better(red_v[i], red_i[i], bv, bi)) { bv = red_v[i]; bi = red_i[i]; bp = red_p[i]; }
         const bool ok = bv > -INFINITY;
         end_state = ok ? bi : -1;
         p.score[b] = ok ? bv : -INFINITY;
@@ -523,30 +480,20 @@ extern "C" size_t oe_ctc_graph_beam_workspace_bytes(int B, int T, int U, int Q, 
 extern "C" int oe_ctc_graph_beam(const oe_ctc_graph_beam_args* args, void* stream) {
     OE_REQUIRE(args, "oe_ctc_graph_beam: null args");
     const oe_ctc_graph_beam_args& a = *args;
-    OE_REQUIRE(a.graph, "oe_ctc_graph_beam: null graph");
+    if (int rc = graph_check("oe_ctc_graph_beam", a.graph, a.logits, a.ldv, a.B, a.T, a.V, a.hlens, a.workspace, &a.max_trav)) return rc;
     const oe_beam_graph& g = *a.graph;
-    OE_REQUIRE(a.logits, "oe_ctc_graph_beam: null logits");
-    OE_REQUIRE(a.hlens, "oe_ctc_graph_beam: null hlens");
     OE_REQUIRE(a.score && a.frames && a.arcs && a.n_trav && a.trav_arc && a.trav_start && a.trav_end && a.status && a.peak,
                "oe_ctc_graph_beam: null output (score, frames, arcs, n_trav, trav_arc, trav_start, trav_end, status, peak)");
-    OE_REQUIRE(a.workspace, "oe_ctc_graph_beam: null workspace");
-    OE_REQUIRE(a.B > 0 && a.T > 0 && a.T <= BEAM_MAX_T && a.V > 1 && a.ldv >= a.V,
-               "oe_ctc_graph_beam: bad shape B=%d T=%d V=%d ldv=%ld (1 <= B, 1 <= T <= 2^20, ldv >= V)", a.B, a.T, a.V, a.ldv);
     OE_REQUIRE(g.Q >= 1 && g.Q <= BEAM_MAX_Q, "oe_ctc_graph_beam: Q=%d nodes outside 1 .. %d", g.Q, BEAM_MAX_Q);
     OE_REQUIRE(g.A >= 1 && g.A <= BEAM_MAX_A, "oe_ctc_graph_beam: A=%d arcs outside 1 .. %d", g.A, BEAM_MAX_A);
-    OE_REQUIRE(g.U >= 1 && g.U < a.V, "oe_ctc_graph_beam: U=%d distinct labels outside 1 .. V-1 = %d", g.U, a.V - 1);
     OE_REQUIRE(g.in_ptr && g.src && g.dst && g.label && g.col && g.w && g.final && g.cols && g.out_ptr && g.out_arc,
                "oe_ctc_graph_beam: null table in graph (in_ptr, src, dst, label, col, w, final, cols, out_ptr, out_arc)");
-    OE_REQUIRE(a.max_trav >= 1, "oe_ctc_graph_beam: max_trav=%d < 1", a.max_trav);
     OE_REQUIRE(a.max_active >= 1, "oe_ctc_graph_beam: max_active=%d < 1", a.max_active);
     OE_REQUIRE(a.beam >= 0.f, "oe_ctc_graph_beam: beam=%g is not >= 0 (+inf: no pruning)", (double)a.beam);
-    OE_REQUIRE((((uintptr_t)a.workspace) & 15) == 0, "oe_ctc_graph_beam: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* cw = reinterpret_cast<float*>(a.workspace);
-    const long rows = (long)a.B * a.T;
-    hipLaunchKernelGGL(beam_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, g.cols, g.U,
-                       a.normalized, cw);
-    OE_LAUNCH_CHECK("ctc_graph_beam_rows");
+    if (int rc = oe_lp_rows("oe_ctc_graph_beam", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, g.cols, g.U, a.normalized, cw, nullptr, st))
+        return rc;
     BeamParams p;
     p.cw = cw;
     p.ws = reinterpret_cast<char*>(a.workspace) + beam_rows_bytes(a.B, a.T, g.U);

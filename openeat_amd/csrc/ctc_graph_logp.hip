@@ -1,8 +1,7 @@
 // Graph CTC likelihood and its gradient: oe_ctc_graph's recursion in the log semiring.  The semantics every layer refers to
 // are in include/openeat_hip.h (oe_ctc_graph_logp).
 //
-//   launch 1  gl_rows_kernel: kws_rows_kernel's row pass (lp as a compact row of U + 1 floats); for the gradient it also keeps
-//             the row's log-sum-exp.
+//   launch 1  lp_rows_kernel (lp_rows.hip): lp as a compact row of U + 1 floats; for the gradient it also keeps the row's log-sum-exp.
 //   launch 2  gl_kernel: ONE WORKGROUP of 1024 threads PER UTTERANCE, the state in LDS as float64 in the log2 domain with a
 //             finite "log 0" (ctc_f64.h's scheme: exp / log in float32 on differences).  A frame is two phases with a barrier
 //             behind each:
@@ -41,49 +40,6 @@
 static_assert(24 * GL_MAX_A + 8 * GL_MAX_Q + 3 * 2 * GL_MAX_HEAVY + 1024 <= 160 * 1024, "oe_ctc_graph_logp: the limits exceed the LDS");
 static_assert(GL_MAX_Q >= 2048 && GL_MAX_A >= 4096, "oe_ctc_graph_logp: the limits are below what its users were promised");
 static_assert(GL_MAX_Q <= 0xffff && GL_MAX_A <= 0xffff, "oe_ctc_graph_logp: the heavy lists hold 16-bit indices");
-
-// ---------------------------------------------------------------- launch 1 ----
-// kws_rows_kernel (ctc_kws.hip) with the row's log-sum-exp kept for the dense pass.
-__global__ __launch_bounds__(256) void gl_rows_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                       const int* __restrict__ hlens, const int* __restrict__ cols, int U,
-                                                       int normalized, float* __restrict__ cw, float* __restrict__ lse) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    float c = 0.f;
-    if (!normalized) {
-        float m = -INFINITY, s = 0.f;
-        int i = lane;
-        for (; i + 7 * 64 < V; i += 8 * 64) {
-            float x[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = p[i + k * 64];
-            float mx = x[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) mx = fmaxf(mx, x[k]);
-            if (mx > m) { s *= expf(m - mx); m = mx; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += expf(x[k] - m);
-        }
-        for (; i < V; i += 64) {
-            const float x = p[i];
-            if (x > m) { s *= expf(m - x); m = x; }
-            s += expf(x - m);
-        }
-        const float wm = wave_max(m);
-        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - wm));
-        c = wm + logf(s);
-    }
-    if (lse && lane == 0) lse[row] = c;
-    float* out = cw + row * (long)(U + 1);
-    for (int u = lane; u <= U; u += 64) {
-        const int col = u == 0 ? 0 : min(max(cols[u - 1], 0), V - 1);       // a label outside [0, V) must not become a wild read
-        out[u] = p[col] - c;
-    }
-}
 
 // ---------------------------------------------------------------- launch 2 ----
 struct GlParams {
@@ -503,11 +459,8 @@ extern "C" int oe_ctc_graph_logp(const oe_ctc_graph_logp_args* args, void* strea
         if (int rc = gl_raise_lds("oe_ctc_graph_logp")) return rc;
     hipStream_t st = (hipStream_t)stream;
     float* cw = reinterpret_cast<float*>(a.workspace);
-    const long rows = (long)a.B * a.T;
-    OE_REQUIRE(rows <= 0x7fffffffL, "oe_ctc_graph_logp: B * T = %ld rows exceed the grid limit", rows);
-    hipLaunchKernelGGL(gl_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, s.cols, s.U,
-                       a.normalized, cw, (float*)nullptr);
-    OE_LAUNCH_CHECK("ctc_graph_logp_rows");
+    if (int rc = oe_lp_rows("oe_ctc_graph_logp", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, s.cols, s.U, a.normalized, cw, nullptr, st))
+        return rc;
     GlParams p = gl_params(s, cw, a.T, a.hlens, a.graph_of);
     p.logp = a.logp;
     hipLaunchKernelGGL(gl_kernel<false>, dim3((unsigned)a.B), dim3(GL_BLOCK), lds, st, p);
@@ -527,8 +480,7 @@ extern "C" int oe_ctc_graph_logp_grad(const oe_ctc_graph_logp_grad_args* args, v
     if (lds > 48 * 1024)
         if (int rc = gl_raise_lds("oe_ctc_graph_logp_grad")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)a.B * a.T;
-    OE_REQUIRE(rows <= 0x7fffffffL, "oe_ctc_graph_logp_grad: B * T = %ld rows exceed the grid limit", rows);
+    const long rows = (long)a.B * a.T;                                       // oe_lp_rows holds them to the grid limit
     char* ws = reinterpret_cast<char*>(a.workspace);
     float* cw = reinterpret_cast<float*>(ws);
     ws += gl_rows_bytes(a.B, a.T, s.U);
@@ -539,9 +491,7 @@ extern "C" int oe_ctc_graph_logp_grad(const oe_ctc_graph_logp_grad_args* args, v
     double* logz = reinterpret_cast<double*>(ws);
     ws += gl_up16((size_t)a.B * 8);
     double* alpha = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(gl_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, s.cols, s.U, 0,
-                       cw, lse);
-    OE_LAUNCH_CHECK("ctc_graph_logp_rows");
+    if (int rc = oe_lp_rows("oe_ctc_graph_logp_grad", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, s.cols, s.U, 0, cw, lse, st)) return rc;
     GlParams p = gl_params(s, cw, a.T, a.hlens, a.graph_of);
     p.logp = a.logp; p.logz = logz; p.alpha = alpha; p.occ = occ;
     hipLaunchKernelGGL(gl_kernel<true>, dim3((unsigned)a.B), dim3(GL_BLOCK), lds, st, p);

@@ -5,7 +5,7 @@
 //
 // A token is 16 bytes: its value, the id of the record of its last "enter an arc" event, and the 64-bit hash of its history.
 // Two launches:
-//   launch 1  graph_nbest_rows_kernel: kws_rows_kernel's row pass, as in ctc_graph.hip.
+//   launch 1  lp_rows_kernel (lp_rows.hip): the blank and the U label columns of every frame as lp, a compact row of U + 1 floats.
 //   launch 2  graph_nbest_kernel<KC, BLOCK>: ONE WORKGROUP PER UTTERANCE, KC in {1, 2, 4, 8} the compiled list capacity
 //             (K <= KC; 1024 threads for KC <= 2, 512 for the longer lists, which then have 256 registers a thread and keep a
 //             list in them).  The token lists do not fit the LDS at the limits; they live in the workspace (L2), the arc
@@ -31,11 +31,11 @@
 //             hypothesis walks its record chain (twice: the length, then the arcs).
 // No workgroup waits for another, no float atomics, no allocation, no host read: capturable.
 #include <stdlib.h>
-#include "oe_common.h"
+#include "ctc_graph_common.h"
 #include "../../include/openeat_hip.h"
 
 #define NB_BLOCK 1024
-#define NB_MAX_T (1 << 20)
+#define NB_MAX_T GRAPH_MAX_T
 #define NB_MAX_A OE_CTC_GRAPH_MAX_ARCS
 #define NB_MAX_Q OE_CTC_GRAPH_MAX_NODES
 #define NB_MAX_K OE_CTC_GRAPH_NBEST_MAX
@@ -56,48 +56,6 @@ __device__ __forceinline__ unsigned long long nb_mix(unsigned long long h, int i
     return z ^ (z >> 31);
 }
 
-// ---------------------------------------------------------------- launch 1 ----
-// kws_rows_kernel (ctc_kws.hip), statement for statement, as graph_rows_kernel (ctc_graph.hip).
-__global__ __launch_bounds__(256) void graph_nbest_rows_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                                const int* __restrict__ hlens, const int* __restrict__ cols, int U,
-                                                                int normalized, float* __restrict__ cw) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    float c = 0.f;
-    if (!normalized) {
-        float m = -INFINITY, s = 0.f;
-        int i = lane;
-        for (; i + 7 * 64 < V; i += 8 * 64) {
-            float x[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = p[i + k * 64];
-            float mx = x[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) mx = fmaxf(mx, x[k]);
-            if (mx > m) { s *= expf(m - mx); m = mx; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += expf(x[k] - m);
-        }
-        for (; i < V; i += 64) {
-            const float x = p[i];
-            if (x > m) { s *= expf(m - x); m = x; }
-            s += expf(x - m);
-        }
-        const float wm = wave_max(m);
-        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - wm));
-        c = wm + logf(s);
-    }
-    float* out = cw + row * (long)(U + 1);
-    for (int u = lane; u <= U; u += 64) {
-        const int col = u == 0 ? 0 : min(max(cols[u - 1], 0), V - 1);       // a label outside [0, V) must not become a wild read
-        out[u] = p[col] - c;
-    }
-}
-
 // ---------------------------------------------------------------- launch 2 ----
 struct NbParams {
     const float* cw;
@@ -107,8 +65,6 @@ struct NbParams {
     const float* w; const float* fin;
     int* n_hyp; float* hyp_score; int* hyp_len; int* hyp_arcs; int* hyp_tokens;
 };
-
-__device__ __forceinline__ bool nb_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
 // A sorted list of at most KC tokens with distinct histories, in registers (every index is static).  aux: the candidate's order
 // key where lists of several lanes are merged, "entered" in phase B.
@@ -222,7 +178,7 @@ __device__ __forceinline__ int nb_select(const NbTok* nprev, float lp0_prev, con
                 const int i = __shfl_xor(bo, o, 64);
                 const int r = __shfl_xor(brec, o, 64);
                 const unsigned long long hh = __shfl_xor(bh, o, 64);
-                if (nb_better(v, i, bv, bo)) { bv = v; bo = i; brec = r; bh = hh; }
+                if (graph_better(v, i, bv, bo)) { bv = v; bo = i; brec = r; bh = hh; }
             }
             if (!(bv > -INFINITY)) done = true;
             else {
@@ -424,13 +380,13 @@ __global__ __launch_bounds__(BLOCK) void graph_nbest_kernel(const NbParams p) {
                 for (int o = 32; o > 0; o >>= 1) {
                     const float v = __shfl_xor(bv, o, 64);
                     const int i = __shfl_xor(bo, o, 64);
-                    if (nb_better(v, i, bv, bo)) { bv = v; bo = i; }
+                    if (graph_better(v, i, bv, bo)) { bv = v; bo = i; }
                 }
                 if (lane == 0) { red_v[wave] = bv; red_i[wave] = bo; }
                 __syncthreads();
                 bv = red_v[0]; bo = red_i[0];
                 for (int i = 1; i < (BLOCK / 64); ++i)
-                    if (nb_better(red_v[i], red_i[i], bv, bo)) { bv = red_v[i]; bo = red_i[i]; }
+                    if (graph_better(red_v[i], red_i[i], bv, bo)) { bv = red_v[i]; bo = red_i[i]; }
                 __syncthreads();
                 if (!(bv > -INFINITY)) done = true;
                 else {
@@ -479,18 +435,12 @@ extern "C" size_t oe_ctc_graph_nbest_workspace_bytes(int B, int T, int U, int Q,
 extern "C" int oe_ctc_graph_nbest(const oe_ctc_graph_nbest_args* args, void* stream) {
     OE_REQUIRE(args, "oe_ctc_graph_nbest: null args");
     const oe_ctc_graph_nbest_args& a = *args;
-    OE_REQUIRE(a.graph, "oe_ctc_graph_nbest: null graph");
+    if (int rc = graph_check("oe_ctc_graph_nbest", a.graph, a.logits, a.ldv, a.B, a.T, a.V, a.hlens, a.workspace, nullptr)) return rc;
     const oe_decoding_graph& g = *a.graph;
-    OE_REQUIRE(a.logits, "oe_ctc_graph_nbest: null logits");
-    OE_REQUIRE(a.hlens, "oe_ctc_graph_nbest: null hlens");
     OE_REQUIRE(a.n_hyp && a.hyp_score && a.hyp_len && a.hyp_arcs && a.hyp_tokens,
                "oe_ctc_graph_nbest: null output (n_hyp, hyp_score, hyp_len, hyp_arcs, hyp_tokens)");
-    OE_REQUIRE(a.workspace, "oe_ctc_graph_nbest: null workspace");
-    OE_REQUIRE(a.B > 0 && a.T > 0 && a.T <= NB_MAX_T && a.V > 1 && a.ldv >= a.V,
-               "oe_ctc_graph_nbest: bad shape B=%d T=%d V=%d ldv=%ld (1 <= B, 1 <= T <= 2^20, ldv >= V)", a.B, a.T, a.V, a.ldv);
     OE_REQUIRE(g.Q >= 1 && g.Q <= NB_MAX_Q, "oe_ctc_graph_nbest: Q=%d nodes outside 1 .. %d", g.Q, NB_MAX_Q);
     OE_REQUIRE(g.A >= 1 && g.A <= NB_MAX_A, "oe_ctc_graph_nbest: A=%d arcs outside 1 .. %d", g.A, NB_MAX_A);
-    OE_REQUIRE(g.U >= 1 && g.U < a.V, "oe_ctc_graph_nbest: U=%d distinct labels outside 1 .. V-1 = %d", g.U, a.V - 1);
     OE_REQUIRE(g.in_ptr && g.src && g.dst && g.label && g.col && g.w && g.final && g.cols,
                "oe_ctc_graph_nbest: null table in graph (in_ptr, src, dst, label, col, w, final, cols)");
     OE_REQUIRE(a.nbest >= 1 && a.nbest <= NB_MAX_K, "oe_ctc_graph_nbest: nbest=%d outside 1 .. %d", a.nbest, NB_MAX_K);
@@ -499,7 +449,6 @@ extern "C" int oe_ctc_graph_nbest(const oe_ctc_graph_nbest_args* args, void* str
                "oe_ctc_graph_nbest: distinct=%d is neither OE_CTC_GRAPH_NBEST_ARCS (0) nor OE_CTC_GRAPH_NBEST_TOKENS (1)", a.distinct);
     OE_REQUIRE((long)a.T * g.A * a.nbest < (1l << 31), "oe_ctc_graph_nbest: T*A*nbest = %ld records, the limit is 2^31 - 1",
                (long)a.T * g.A * a.nbest);
-    OE_REQUIRE((((uintptr_t)a.workspace) & 15) == 0, "oe_ctc_graph_nbest: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const size_t B = (size_t)a.B, T = (size_t)a.T, Q = (size_t)g.Q, A = (size_t)g.A, K = (size_t)a.nbest;
     NbParams p;
@@ -510,10 +459,8 @@ extern "C" int oe_ctc_graph_nbest(const oe_ctc_graph_nbest_args* args, void* str
     p.recs = p.alt_col + B * Q * K;
     float* cw = reinterpret_cast<float*>(p.recs + B * T * A * K);
     p.cw = cw;
-    const long rows = (long)a.B * a.T;
-    hipLaunchKernelGGL(graph_nbest_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, g.cols,
-                       g.U, a.normalized, cw);
-    OE_LAUNCH_CHECK("ctc_graph_nbest_rows");
+    if (int rc = oe_lp_rows("oe_ctc_graph_nbest", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, g.cols, g.U, a.normalized, cw, nullptr, st))
+        return rc;
     p.T = a.T; p.U = g.U; p.Q = g.Q; p.A = g.A; p.K = a.nbest; p.max_len = a.max_len; p.tokens_mode = a.distinct == OE_CTC_GRAPH_NBEST_TOKENS;
     p.hlens = a.hlens; p.in_ptr = g.in_ptr; p.src = g.src; p.dst = g.dst; p.label = g.label; p.col = g.col; p.w = g.w; p.fin = g.final;
     p.n_hyp = a.n_hyp; p.hyp_score = a.hyp_score; p.hyp_len = a.hyp_len; p.hyp_arcs = a.hyp_arcs; p.hyp_tokens = a.hyp_tokens;

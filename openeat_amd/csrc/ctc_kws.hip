@@ -3,11 +3,7 @@
 //
 // A keyword is at most 32 labels, 63 states: one wave holds its trellis column, a state per lane.  What is large is the
 // product: K ~ 1000 keywords x T ~ 90 000 frames x V ~ 4000 columns.  Two launches:
-//   launch 1  kws_rows_kernel: one wave per frame (as seg_rows_kernel).  The row is read once, coalesced, with its log-sum-exp
-//             c_t taken on the way (one pass: a running maximum and a rescaled sum per lane, merged across the wave), and the
-//             blank and the U keyword columns are gathered from the row just read (L1 / L2 hits) and written as
-//             lp = x - c_t into a compact row of U + 1 floats.  normalized: no pass over the row, the gather alone.
-//             Bound: the logits' bytes from HBM, once.
+//   launch 1  lp_rows_kernel (lp_rows.hip): the blank and the U keyword columns of every frame as lp, a compact row of U + 1 floats.
 //   launch 2  kws_kernel: ONE WAVE PER (recording, keyword), KWS_KPW keywords of the same recording per workgroup so that the
 //             compact rows their lanes gather share cache lines in the CU's L1.  Lane s-1 holds state s: its value v and the
 //             frame st at which its path entered state 1.  v and st reach lane+1 by one wave shift (kws_shr1, as seg_shr1) and
@@ -36,48 +32,6 @@ __device__ __forceinline__ float kws_shr1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, KWS_NEG), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
 }
 __device__ __forceinline__ int kws_shr1(int v) { return __builtin_amdgcn_update_dpp(-1, v, 0x138, 0xf, 0xf, false); }
-
-// ---------------------------------------------------------------- launch 1 ----
-__global__ __launch_bounds__(256) void kws_rows_kernel(const float* __restrict__ logits, long ldv, long rows, int T, int V,
-                                                        const int* __restrict__ hlens, const int* __restrict__ cols, int U,
-                                                        int normalized, float* __restrict__ cw) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = (int)(row / T), t = (int)(row % T);
-    if (t >= hlens[b]) return;
-    const float* p = logits + row * ldv;
-    float c = 0.f;
-    if (!normalized) {
-        // one pass: per lane a running maximum m and the sum of exp(x - m), eight elements in flight
-        float m = -INFINITY, s = 0.f;
-        int i = lane;
-        for (; i + 7 * 64 < V; i += 8 * 64) {
-            float x[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = p[i + k * 64];
-            float mx = x[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) mx = fmaxf(mx, x[k]);
-            if (mx > m) { s *= expf(m - mx); m = mx; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += expf(x[k] - m);
-        }
-        for (; i < V; i += 64) {
-            const float x = p[i];
-            if (x > m) { s *= expf(m - x); m = x; }
-            s += expf(x - m);
-        }
-        const float wm = wave_max(m);
-        s = wave_sum(m == -INFINITY ? 0.f : s * expf(m - wm));
-        c = wm + logf(s);
-    }
-    float* out = cw + row * (long)(U + 1);
-    for (int u = lane; u <= U; u += 64) {
-        const int col = u == 0 ? 0 : min(max(cols[u - 1], 0), V - 1);       // a label outside [0, V) must not become a wild read
-        out[u] = p[col] - c;
-    }
-}
 
 // ---------------------------------------------------------------- launch 2 ----
 struct KwsParams {
@@ -231,10 +185,8 @@ extern "C" int oe_ctc_kws(const oe_ctc_kws_args* args, void* stream) {
     OE_REQUIRE((long)a.B * nkb <= 0x7fffffffL, "oe_ctc_kws: B=%d x K=%d exceeds one launch's workgroups", a.B, q.K);
     hipStream_t st = (hipStream_t)stream;
     float* cw = reinterpret_cast<float*>(a.workspace);
-    const long rows = (long)a.B * a.T;
-    hipLaunchKernelGGL(kws_rows_kernel, dim3(oe_cdiv(rows, 4)), dim3(256), 0, st, a.logits, a.ldv, rows, a.T, a.V, a.hlens, q.cols, q.U,
-                       a.normalized, cw);
-    OE_LAUNCH_CHECK("ctc_kws_rows");
+    if (int rc = oe_lp_rows("oe_ctc_kws", a.logits, a.ldv, a.B, a.T, a.V, a.hlens, q.cols, q.U, a.normalized, cw, nullptr, st))
+        return rc;
     KwsParams p;
     p.cw = cw; p.T = a.T; p.U = q.U; p.K = q.K; p.Lmax = q.Lmax; p.max_hits = a.max_hits;
     p.hlens = a.hlens; p.kw_col = q.kw_col; p.klens = q.klens; p.thr = q.thr;

@@ -30,6 +30,11 @@ extern "C" void oe_set_error(const char* fmt, ...);
 
 static inline int oe_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// launch 1 of the keyword and graph CTC decoders (lp_rows.hip): lp of the blank and of the U columns `cols` of every frame
+// t < hlens[b] into cw (rows of U + 1 floats), the row's log-sum-exp into lse if given.  Returns 0, or the error, set.
+int oe_lp_rows(const char* who, const float* logits, long ldv, int B, int T, int V, const int* hlens, const int* cols, int U,
+               int normalized, float* cw, float* lse, hipStream_t st);
+
 // ---- wave-level reductions (64 lanes) --------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

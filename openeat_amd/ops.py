@@ -2446,6 +2446,31 @@ def ctc_keyword_search(logits, hlens, keywords, max_hits=8, normalized=False, ma
     return outs
 
 
+def _graph_decode_front(name, logits, hlens, graph):
+    """What the graph decoders' wrappers do first: graph's type, logits (B, T, V) float32 on the device and contiguous ->
+    (logits, hl32, (B, T, V), (U, Q, A))."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph
+    if not isinstance(graph, DecodingGraph):
+        raise TypeError(f"{name}: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    logits = _chk(logits, name)
+    if logits.dim() != 3:
+        raise ValueError(f"{name}: logits must be (B, T, V), got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    hl32 = hlens.to(device=logits.device, dtype=torch.int32).contiguous()
+    return logits, hl32, tuple(logits.shape), (len(graph.cols), graph.num_nodes, graph.num_arcs)
+
+
+def _graph_decode_groups(make_args, logits, hl32, g, ws, group):
+    """The utterances in consecutive groups of at most `group`: (args, lo) per group, args with the fields every graph decoder
+    has filled in for the utterances lo .. lo+n-1 (those rows of every (B, ..) tensor are dense), one workspace reused."""
+    B, T, V = logits.shape
+    for lo in range(0, B, group):
+        a = make_args()
+        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, min(group, B - lo), T, V
+        a.hlens, a.graph, a.workspace = hl32[lo:].data_ptr(), hip.C.pointer(g), ws.data_ptr()
+        yield a, lo
+
+
 def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, workspace_cap=1 << 30):
     """Grammar-constrained CTC decoding (oe_ctc_graph; semantics in include/openeat_hip.h): logits (B, T, V) float32 (raw, or
     log-probabilities with normalized=True), hlens (B), graph an openeat_amd.utils.decoding_graph.DecodingGraph -> device
@@ -2454,22 +2479,13 @@ def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, work
     is 4 * T * (U + 1 + Q + ceil(A / 4)) bytes per utterance; where that exceeds workspace_cap for the batch the utterances -
     they are independent - run in consecutive groups of as many as fit (at least one), one workspace reused: exactly the
     results of one call."""
-    from openeat_amd.utils.decoding_graph import DecodingGraph
-    if not isinstance(graph, DecodingGraph):
-        raise TypeError(f"ctc_graph_decode: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
-    logits = _chk(logits, "ctc_graph_decode")
-    if logits.dim() != 3:
-        raise ValueError(f"ctc_graph_decode: logits must be (B, T, V), got {tuple(logits.shape)}")
-    logits = logits.contiguous()
-    B, T, V = logits.shape
+    logits, hl32, (B, T, V), (U, Q, A) = _graph_decode_front("ctc_graph_decode", logits, hlens, graph)
     dev = logits.device
     max_trav = T if max_trav is None else int(max_trav)
-    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
     per_utt = hip.lib().oe_ctc_graph_workspace_bytes(1, T, U, Q, A) if B >= 1 else 0
     if per_utt == 0 or max_trav < 1 or U >= V:
         raise ValueError(f"ctc_graph_decode: B={B} T={T} max_trav={max_trav} U={U} V={V} Q={Q} A={A} outside 1 <= B, 1 <= T <= 2^20, "
                          "1 <= max_trav, 1 <= U < V, 1 <= Q <= 8064, 1 <= A <= 16384 (a graph without arcs has no device form)")
-    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
     score = torch.empty(B, dtype=torch.float32, device=dev)
     frames = torch.empty(B, T, dtype=torch.int32, device=dev)
     arcs = torch.empty(B, T, dtype=torch.int32, device=dev)
@@ -2482,16 +2498,10 @@ def ctc_graph_decode(logits, hlens, graph, normalized=False, max_trav=None, work
     outs = (score, frames, arcs, path_logp, n_trav, trav_arc, trav_start, trav_end, trav_logp)
     group = min(max(int(workspace_cap) // per_utt, 1), B)
     ws = torch.empty(per_utt * group, dtype=torch.uint8, device=dev)
-    g = hip.decoding_graph(graph, dev)
-    for lo in range(0, B, group):
-        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
-        a = hip.CtcGraphArgs()
-        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
-        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+    for a, lo in _graph_decode_groups(hip.CtcGraphArgs, logits, hl32, hip.decoding_graph(graph, dev), ws, group):
         a.normalized, a.max_trav = int(bool(normalized)), max_trav
         a.score, a.frames, a.arcs, a.path_logp = (t[lo:].data_ptr() for t in outs[:4])
         a.n_trav, a.trav_arc, a.trav_start, a.trav_end, a.trav_logp = (t[lo:].data_ptr() for t in outs[4:])
-        a.workspace = ws.data_ptr()
         hip.check(hip.lib().oe_ctc_graph(hip.C.byref(a), hip.stream()), "oe_ctc_graph")
     return outs
 
@@ -2505,21 +2515,13 @@ def ctc_graph_nbest(logits, hlens, graph, nbest, distinct="arcs", normalized=Fal
     is dominated by the record table, 4 * T * A * nbest bytes per utterance; where the batch exceeds workspace_cap the
     utterances - they are independent - run in consecutive groups of as many as fit, one workspace reused: exactly the results
     of one call.  One utterance alone above the cap is a ValueError that names the bytes."""
-    from openeat_amd.utils.decoding_graph import DecodingGraph
-    if not isinstance(graph, DecodingGraph):
-        raise TypeError(f"ctc_graph_nbest: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    logits, hl32, (B, T, V), (U, Q, A) = _graph_decode_front("ctc_graph_nbest", logits, hlens, graph)
     modes = {"arcs": hip.CTC_GRAPH_NBEST_ARCS, "tokens": hip.CTC_GRAPH_NBEST_TOKENS}
     if distinct not in modes:
         raise ValueError(f"ctc_graph_nbest: distinct is 'arcs' or 'tokens', got {distinct!r}")
-    logits = _chk(logits, "ctc_graph_nbest")
-    if logits.dim() != 3:
-        raise ValueError(f"ctc_graph_nbest: logits must be (B, T, V), got {tuple(logits.shape)}")
-    logits = logits.contiguous()
-    B, T, V = logits.shape
     dev = logits.device
     nbest = int(nbest)
     max_len = T if max_len is None else int(max_len)
-    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
     lib = hip.lib()
     per_utt = lib.oe_ctc_graph_nbest_workspace_bytes(1, T, U, Q, A, nbest) if B >= 1 else 0
     if per_utt == 0 or max_len < 1 or U >= V:
@@ -2528,7 +2530,6 @@ def ctc_graph_nbest(logits, hlens, graph, nbest, distinct="arcs", normalized=Fal
     if per_utt > int(workspace_cap):
         raise ValueError(f"ctc_graph_nbest: one utterance needs a workspace of {per_utt} bytes (T={T} A={A} nbest={nbest}: the record "
                          f"table alone is {4 * T * A * nbest}), above workspace_cap={int(workspace_cap)}")
-    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
     n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
     hyp_score = torch.empty(B, nbest, dtype=torch.float32, device=dev)
     hyp_len = torch.empty(B, nbest, dtype=torch.int32, device=dev)
@@ -2537,15 +2538,9 @@ def ctc_graph_nbest(logits, hlens, graph, nbest, distinct="arcs", normalized=Fal
     outs = (n_hyp, hyp_score, hyp_len, hyp_arcs, hyp_tokens)
     group = min(int(workspace_cap) // per_utt, B)
     ws = torch.empty(lib.oe_ctc_graph_nbest_workspace_bytes(group, T, U, Q, A, nbest), dtype=torch.uint8, device=dev)
-    g = hip.decoding_graph(graph, dev)
-    for lo in range(0, B, group):
-        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
-        a = hip.CtcGraphNbestArgs()
-        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
-        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+    for a, lo in _graph_decode_groups(hip.CtcGraphNbestArgs, logits, hl32, hip.decoding_graph(graph, dev), ws, group):
         a.normalized, a.nbest, a.distinct, a.max_len = int(bool(normalized)), nbest, modes[distinct], max_len
         a.n_hyp, a.hyp_score, a.hyp_len, a.hyp_arcs, a.hyp_tokens = (t[lo:].data_ptr() for t in outs)
-        a.workspace = ws.data_ptr()
         hip.check(lib.oe_ctc_graph_nbest(hip.C.byref(a), hip.stream()), "oe_ctc_graph_nbest")
     return outs
 
@@ -2559,42 +2554,27 @@ def ctc_graph_beam_decode(logits, hlens, graph, beam, max_active=16384, normaliz
     The workspace is 4 * T * (U + 1) bytes of rows and 40 Q + 20 A + (28 + 8 T) min(max_active, Q + A) bytes of state per
     utterance; where that exceeds workspace_cap for the batch the utterances run in consecutive groups of as many as fit (at
     least one), one workspace reused: exactly the results of one call.  No host read."""
-    from openeat_amd.utils.decoding_graph import DecodingGraph
-    if not isinstance(graph, DecodingGraph):
-        raise TypeError(f"ctc_graph_beam_decode: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
-    logits = _chk(logits, "ctc_graph_beam_decode")
-    if logits.dim() != 3:
-        raise ValueError(f"ctc_graph_beam_decode: logits must be (B, T, V), got {tuple(logits.shape)}")
-    logits = logits.contiguous()
-    B, T, V = logits.shape
+    logits, hl32, (B, T, V), (U, Q, A) = _graph_decode_front("ctc_graph_beam_decode", logits, hlens, graph)
     dev = logits.device
     max_trav = T if max_trav is None else int(max_trav)
     beam, max_active = float(beam), int(max_active)
-    U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
     lib = hip.lib()
     per_utt = lib.oe_ctc_graph_beam_workspace_bytes(1, T, U, Q, A, max_active) if B >= 1 and 1 <= max_active < 1 << 31 else 0
     if per_utt == 0 or max_trav < 1 or U >= V or not beam >= 0:
         raise ValueError(f"ctc_graph_beam_decode: B={B} T={T} max_trav={max_trav} max_active={max_active} beam={beam} U={U} V={V} Q={Q} "
                          f"A={A} outside 1 <= B, 1 <= T <= 2^20, 1 <= max_trav, 1 <= max_active, 0 <= beam, 1 <= U < V, 1 <= Q <= 2^20, "
                          "1 <= A <= 2^22 (a graph without arcs has no device form)")
-    hl32 = hlens.to(device=dev, dtype=torch.int32).contiguous()
     i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
     f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     outs = (f32(B), i32(B, T), i32(B, T), f32(B, T), i32(B), i32(B, max_trav), i32(B, max_trav), i32(B, max_trav), f32(B, max_trav),
             i32(B), i32(B))
     group = min(max(int(workspace_cap) // per_utt, 1), B)
     ws = torch.empty(lib.oe_ctc_graph_beam_workspace_bytes(group, T, U, Q, A, max_active), dtype=torch.uint8, device=dev)
-    g = hip.beam_graph(graph, dev)
-    for lo in range(0, B, group):
-        n = min(group, B - lo)                                     # rows lo .. lo+n-1 of every (B, ..) tensor are dense
-        a = hip.CtcGraphBeamArgs()
-        a.logits, a.ldv, a.B, a.T, a.V = logits[lo].data_ptr(), V, n, T, V
-        a.hlens, a.graph = hl32[lo:].data_ptr(), hip.C.pointer(g)
+    for a, lo in _graph_decode_groups(hip.CtcGraphBeamArgs, logits, hl32, hip.beam_graph(graph, dev), ws, group):
         a.normalized, a.max_trav, a.max_active, a.beam = int(bool(normalized)), max_trav, max_active, beam
         a.score, a.frames, a.arcs, a.path_logp = (t[lo:].data_ptr() for t in outs[:4])
         a.n_trav, a.trav_arc, a.trav_start, a.trav_end, a.trav_logp = (t[lo:].data_ptr() for t in outs[4:9])
         a.status, a.peak = outs[9][lo:].data_ptr(), outs[10][lo:].data_ptr()
-        a.workspace = ws.data_ptr()
         hip.check(lib.oe_ctc_graph_beam(hip.C.byref(a), hip.stream()), "oe_ctc_graph_beam")
     return outs
 

@@ -11,7 +11,7 @@ Synthetic logits: randn with +14 on a planted frame labelling that speaks phrase
 call is also checked at the size it is timed at: token_loop and trie_loop must return the planted tokens.
 
 Timed with HIP events alone, median of 5 calls after a warm-up call, three runs (the machine is shared), the middle one
-reported.  Launch 1 is kws_rows_kernel statement for statement, so it is timed through oe_ctc_kws with the graph's columns and
+reported.  Launch 1 is oe_ctc_kws's (lp_rows_kernel, one kernel for both), so it is timed through oe_ctc_kws with the graph's columns and
 every keyword empty (its launch 2 then only writes empty results); launch 2 is the full call minus that.  `floor` is launch 2
 on a graph of one self-loop with the same columns: Tb frames of two barriers each and the fixed parts (end arg-max,
 back-trace, traversal scan) with next to no state to update.  oe_ctc_align on the same logits, each utterance aligned to its

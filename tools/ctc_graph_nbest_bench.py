@@ -9,7 +9,7 @@ The shape of tools/ctc_graph_decode_bench.py, B = 32 utterances of T = 250 frame
   lexicon      1000 words of 3 labels, each a chain of its own from the start node back to it: one node with 1000 arcs in
                and 1000 out, no shared prefixes
 For K = 1, 2, 4, 8 and both `distinct` modes the call is timed with HIP events (median of 5 after a warm-up, three runs, the
-middle one); launch 1 is kws_rows_kernel statement for statement and is timed alone through oe_ctc_kws, as the decode bench
+middle one); launch 1 is oe_ctc_kws's (lp_rows_kernel, one kernel for both) and is timed alone through oe_ctc_kws, as the decode bench
 does, so the recursion launch is the call minus that.  oe_ctc_graph at the same shape stands beside it: the dense kernel is
 the yardstick, and `ratio` is recursion launch / dense recursion launch.  The call is also checked at the size it is timed at:
 with K = 1 the score and the arcs must be oe_ctc_graph's, and on trie_loop rank 0 must spell the planted tokens.  One JSON line."""
