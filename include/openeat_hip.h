@@ -876,6 +876,121 @@ size_t oe_ctc_graph_logp_grad_workspace_bytes(int B, int T, int U, int Qmax, int
 int oe_ctc_graph_logp(const oe_ctc_graph_logp_args* args, void* stream);
 int oe_ctc_graph_logp_grad(const oe_ctc_graph_logp_grad_args* args, void* stream);
 
+/* Beam-pruned graph CTC likelihood on device over large token graphs: the sum half of oe_ctc_graph_beam.  logZ = the log of the
+ * sum over every path of the graph that survives a beam, and its gradient with respect to raw logits: the rejection score, the
+ * best-path posterior, the graph loss and the MMI denominator of a lexicon loop of 10^5 words, a phrase book, a bigram grammar -
+ * the graphs oe_ctc_graph_logp cannot hold in LDS.  These are the semantics every layer refers to.
+ *   Shared: the graph, the node states n[q] and arc states r[a], lp, Tb and the clamping of labels and indices are
+ *   oe_ctc_graph's; the recursion is oe_ctc_graph_logp's: every "best of" is a log-sum-exp, parallel arcs both count.
+ *   Beam: beam is a float32, >= 0 or +inf.  After the values (alpha) of frame t are made, for every t < Tb-1: best_t = the
+ *   maximum over all node and arc values, thr_t = best_t - beam, and every state with alpha < thr_t becomes unreachable before
+ *   frame t+1 reads it; a state equal to thr_t survives.  The last frame is not pruned.  S_t = the survivors of frame t.
+ *   logZ = LSE over S_{Tb-1} of alpha + final, as in oe_ctc_graph_logp.  (The comparison runs on the kernel's float64 log2-domain
+ *   values; a state within rounding of a threshold may fall on either side.)
+ *   Capacity, status, peak, overflow: oe_ctc_graph_beam's, word for word, with OE_CTC_GRAPH_BEAM_OK / _INFEASIBLE / _OVERFLOW.
+ *   An overflowed or infeasible utterance has logp = -inf exactly and exact-zero gradient rows; its g is never read into a result.
+ *   Gradient (raw logits only; normalized != 0 is an error): the derivative of logZ with the survivor sets held fixed, which is
+ *   the true derivative wherever no value sits on a threshold.  beta on the sub-lattice: beta_{Tb-1} is oe_ctc_graph_logp's end
+ *   rule on S_{Tb-1}; beta_t[s] for s in S_t sums only over successors in S_{t+1}; beta_t[s] = "log 0" for s not in S_t.
+ *   occ[t,v] = the sum over the states of label v in S_t of exp(alpha + beta - logZ); each occ row sums to 1 (a float64
+ *   restatement measured row-sum errors <= 3e-14).  dlogits = g[b] * (occ - softmax) for t < Tb; rows t >= Tb are exact zeros;
+ *   columns >= V are never written.
+ *   With beam = +inf, max_active >= Q + A and a graph inside oe_ctc_graph_logp's limits, logp and dlogits agree with
+ *   oe_ctc_graph_logp and oe_ctc_graph_logp_grad within the tolerances below - not bit for bit: the arithmetic differs.
+ *   Every output is bit-identical from run to run and those of utterance b depend on utterance b alone; the order in which
+ *   threads append to a list reaches no output.
+ *   oe_ctc_graph_beam_logp: logp (B) float32, status (B), peak (B) int32 out.  oe_ctc_graph_beam_logp_grad: g (B) float32 in;
+ *   dlogits (B, T, ldv) out, which may not alias logits; status, peak out; logp (B) out or NULL, bit-identical to the score
+ *   call's.  It runs the forward sweep itself; nothing is handed over from the score call.
+ *   The graph is one struct, oe_beam_logp_graph: the tables of oe_beam_graph and the label groups the sum needs, per arc
+ *   (openeat_amd/utils/decoding_graph.py builds them once on the host; group ids are those of oe_graph_set for a set of this
+ *   one graph): in_grp (A) = the in-group of dst[a] that holds a; out_grp (A) = the out-group of src[a] that holds a; in_xg,
+ *   out_xg (A) as in oe_graph_set; inv (n_inv) as in oe_graph_set.  Host memory read during the call only, its pointers device
+ *   pointers.
+ *   Numbers: the state is float64 in the log2 domain with a finite "log 0", exp / log float32 on differences, as in
+ *   oe_ctc_graph_logp.  A sum over the arcs into a node is pushed by many threads and must not depend on their order: per
+ *   touched node v1 / c1 (the greatest incoming value up to a float32 rounding, its label) and v2 (likewise among the arcs of
+ *   another label than c1) by 64-bit integer atomicMax on oe_ctc_graph_beam's keys; then every alive incoming arc adds
+ *   exp2(v - v1) as a 64-bit fixed-point integer at scale 2^40 to a per-node total S1 and, if its label is not c1, to its
+ *   (node, label) group slot G and exp2(v - v2) to S2.  Integer adds are associative; 2^22 terms of at most 2^41 cannot
+ *   overflow.  "Every incoming arc of another label" for a leaving arc of label c is S2 (scaled by v2) if c == c1, else the
+ *   exact integer difference S1 - G[c], which always contains v1's term: never a cancellation, the sum of the other groups to
+ *   2^-40 of the largest.  beta is the mirror image over the out-groups; the occupancies add as fixed-point integers into a
+ *   row of U + 1 per frame; logZ is a maximum over the last list and one more fixed-point sum.
+ *   Against the float64 restatement (tests/ctc_graph_beam_logp_ref.py): oe_ctc_graph_logp's tolerances, logp rtol 1e-4 / atol
+ *   1e-3, gradient rtol 2e-3 / atol 2e-5 * |g[b]|.  Worst observed (tests/test_ctc_graph_beam_logp_gpu.py, one MI355X): 0.0008
+ *   of the logp tolerance and 0.042 of the gradient's (a token loop, V = 300, beam = inf); with a beam 0.0008 / 0.0097 (a
+ *   lexicon loop of 5403 nodes and 10402 arcs, beams 10 and 14).  A pruned comparison is discrete - a state within rounding
+ *   of a threshold may fall on either side - so the tests compare where the restatement is insensitive to the beam.
+ *   Limits: B, T, V, ldv, U, max_active and beam as in oe_ctc_graph_beam; 1 <= Q <= OE_CTC_GRAPH_BEAM_MAX_NODES, 1 <= A <=
+ *   OE_CTC_GRAPH_BEAM_MAX_ARCS.  Anything else, any NULL required pointer (logits, hlens, graph and its tables - inv may be
+ *   NULL where n_inv == 0 -, logp for the score, g and dlogits for the gradient, status, peak, workspace), a workspace not
+ *   16-byte aligned, and dlogits == logits are reported through oe_last_error before any launch, with the outputs untouched.
+ *   The size functions return 0 outside the limits.
+ *   workspace, 16-byte aligned.  With M = min(max_active, Q + A), Q', A', M', T' = Q, A, M, T rounded up to a multiple of 4 and
+ *   R = ceil16(4 * B * T * (U + 1)), the lp rows of oe_ctc_kws:
+ *   oe_ctc_graph_beam_logp_workspace_bytes(B,T,U,Q,A,max_active) =
+ *     R + B * (52 * Q'   per node: two push keys, S1, S2 (8 each), value (8), stamp, touch stamp, a candidate slot (4 each)
+ *            + 24 * A'   per arc: group slot G (8), value (8), stamp, a candidate slot
+ *            + 60 * M')  per frame, reused: the touched nodes, the wide ones, five 8-byte aggregates and c1 per touched node,
+ *                        and two active lists of state ids used in turn
+ *   oe_ctc_graph_beam_logp_grad_workspace_bytes(B,T,U,Q,A,max_active) =
+ *     3 * R              the lp rows, and the occupancy rows as 64-bit fixed point
+ *     + ceil16(4 * B * T) + ceil16(8 * B)   the rows' log-sum-exp, logZ
+ *     + B * (64 * Q' + 36 * A'   as above, and beta with its stamp per node and per arc
+ *            + 60 * M'           as above, with a buffer of new betas in place of the two lists
+ *            + 4 * T'            the survivor count of each frame
+ *            + 12 * T * M')      per frame, kept: state id and alpha of each survivor
+ *   No T * Q or T * A term: the graph's size is paid once per utterance, a frame costs O(survivors + their out-arcs) - a hub's
+ *   in-arcs are never walked.  Utterances are independent, so a caller short of memory runs them in groups.
+ * Launches: the row pass of oe_ctc_kws; one workgroup of 1024 threads per utterance (score: the forward sweep; gradient:
+ * forward, the backward sweep over the stored lists, the occupancies); for the gradient one dense pass over the dlogits rows.
+ * No workgroup waits for another, no float atomics; no allocation, no host read, no host-side state: capturable. */
+typedef struct oe_beam_logp_graph {
+    int Q, A;
+    const int* in_ptr;    /* (Q+1) the arcs into q are in_ptr[q] .. in_ptr[q+1]-1 */
+    const int* src;       /* (A) */
+    const int* dst;       /* (A) ascending */
+    const int* label;     /* (A) */
+    const int* col;       /* (A) index of label[a] into cols */
+    const float* w;       /* (A) */
+    const float* final;   /* (Q) -inf: not final */
+    const int* cols;      /* (U) the distinct labels, ascending */
+    int U;
+    const int* out_ptr;   /* (Q+1) the arcs leaving q are out_arc[out_ptr[q] .. out_ptr[q+1]-1] */
+    const int* out_arc;   /* (A) arc ids ordered by (src, id) */
+    const int* in_grp;    /* (A) the in-group of dst[a] that holds a */
+    const int* in_xg;     /* (A) the in-group of src[a] that carries col[a], or -1 */
+    const int* out_grp;   /* (A) the out-group of src[a] that holds a */
+    const int* out_xg;    /* (A) the out-group of dst[a] that carries col[a], or -1 */
+    const int* inv;       /* (n_inv) */
+    int n_inv;
+} oe_beam_logp_graph;
+typedef struct oe_ctc_graph_beam_logp_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_beam_logp_graph* graph;
+    int normalized, max_active;
+    float beam;
+    float* logp; int* status; int* peak;
+    void* workspace;
+} oe_ctc_graph_beam_logp_args;
+typedef struct oe_ctc_graph_beam_logp_grad_args {
+    const float* logits; long ldv; int B, T, V;
+    const int* hlens;
+    const oe_beam_logp_graph* graph;
+    int normalized, max_active;
+    float beam;
+    const float* g;
+    float* dlogits;
+    float* logp; int* status; int* peak;
+    void* workspace;
+} oe_ctc_graph_beam_logp_grad_args;
+size_t oe_ctc_graph_beam_logp_workspace_bytes(int B, int T, int U, int Q, int A, int max_active);
+size_t oe_ctc_graph_beam_logp_grad_workspace_bytes(int B, int T, int U, int Q, int A, int max_active);
+int oe_ctc_graph_beam_logp(const oe_ctc_graph_beam_logp_args* args, void* stream);
+int oe_ctc_graph_beam_logp_grad(const oe_ctc_graph_beam_logp_grad_args* args, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Fused multi-head attention (scores -> mask -> softmax -> 0-fill -> dropout
  * -> .V), forward and backward, for attention.py:65-97,112-117,189-209.

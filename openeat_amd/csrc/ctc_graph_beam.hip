@@ -41,8 +41,6 @@
 #define BEAM_WIDE 16                              // a node of more leaving arcs than this takes a wave, not a thread
 #define BEAM_NONE 0x7fffffff
 
-typedef unsigned long long beam_u64;
-
 // ---------------------------------------------------------------- launch 2 ----
 // The per-utterance workspace: byte offsets of its parts, every one a multiple of 16 (Q, A, M are rounded up to 4).
 struct BeamLayout {
@@ -88,28 +86,6 @@ struct BeamParams {
     int* n_trav; int* trav_arc; int* trav_start; int* trav_end; float* trav_logp;
     int* status; int* peak;
 };
-
-// (value, arc id) -> a key whose unsigned order is "greater value, then lower id"; 0 is below every key.  -0 and +0 are one value.
-__device__ __forceinline__ beam_u64 beam_key(float v, int id) {
-    const unsigned u = __float_as_uint(v + 0.f);
-    const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((beam_u64)o << 32) | (unsigned)~id;
-}
-__device__ __forceinline__ int beam_key_id(beam_u64 k) { return (int)~(unsigned)k; }
-__device__ __forceinline__ beam_u64 beam_load(const beam_u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void beam_clear(beam_u64* p) { __hip_atomic_store(p, (beam_u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// A slot in a list for every lane that wants one, one add per wave.  Called by whole waves only (uniform control flow).
-__device__ __forceinline__ int beam_append(int* counter, bool want) {
-    const beam_u64 m = __ballot(want);
-    if (m == 0) return -1;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)m) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(counter, __popcll(m));
-    base = __shfl(base, leader, 64);
-    return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-}
 
 __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const BeamParams p) {
     __shared__ int s_ntouched, s_nwide, s_ncand, s_nsurv;

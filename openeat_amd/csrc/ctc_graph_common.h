@@ -1,5 +1,5 @@
-// What the graph CTC decoders share (ctc_graph.hip, ctc_graph_beam.hip, ctc_graph_nbest.hip): the tie rule and the host checks their
-// entries have in common.
+// What the graph CTC kernels share (ctc_graph.hip, ctc_graph_beam.hip, ctc_graph_nbest.hip, ctc_graph_beam_logp.hip): the tie rule, the
+// push key and the list append of the token-passing kernels, and the host checks their entries have in common.
 #pragma once
 #include "oe_common.h"
 
@@ -7,6 +7,30 @@
 
 // the tie rule (oe_ctc_align's, generalised): the greater value, the lower index among equal values
 __device__ __forceinline__ bool graph_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+typedef unsigned long long beam_u64;
+
+// (value, arc id) -> a key whose unsigned order is "greater value, then lower id"; 0 is below every key.  -0 and +0 are one value.
+__device__ __forceinline__ beam_u64 beam_key(float v, int id) {
+    const unsigned u = __float_as_uint(v + 0.f);
+    const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((beam_u64)o << 32) | (unsigned)~id;
+}
+__device__ __forceinline__ int beam_key_id(beam_u64 k) { return (int)~(unsigned)k; }
+__device__ __forceinline__ beam_u64 beam_load(const beam_u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void beam_clear(beam_u64* p) { __hip_atomic_store(p, (beam_u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// A slot in a list for every lane that wants one, one add per wave.  Called by whole waves only (uniform control flow).
+__device__ __forceinline__ int beam_append(int* counter, bool want) {
+    const beam_u64 m = __ballot(want);
+    if (m == 0) return -1;
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(counter, __popcll(m));
+    base = __shfl(base, leader, 64);
+    return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+}
 
 // The checks the decoders' entries share; graph: oe_decoding_graph or oe_beam_graph.  max_trav: null where the entry has none.
 template <class Graph>

@@ -278,6 +278,29 @@ class CtcGraphBeamArgs(C.Structure):
                 ("status", c_fp), ("peak", c_fp), ("workspace", c_fp)]
 
 
+class BeamLogpGraph(C.Structure):
+    """oe_beam_logp_graph (include/openeat_hip.h); filled by beam_logp_graph."""
+    _fields_ = [("Q", C.c_int), ("A", C.c_int), ("in_ptr", c_fp), ("src", c_fp), ("dst", c_fp), ("label", c_fp), ("col", c_fp),
+                ("w", c_fp), ("final", c_fp), ("cols", c_fp), ("U", C.c_int), ("out_ptr", c_fp), ("out_arc", c_fp),
+                ("in_grp", c_fp), ("in_xg", c_fp), ("out_grp", c_fp), ("out_xg", c_fp), ("inv", c_fp), ("n_inv", C.c_int)]
+
+
+class CtcGraphBeamLogpArgs(C.Structure):
+    """oe_ctc_graph_beam_logp_args (include/openeat_hip.h); filled by ops.ctc_graph_beam_logp.  A struct assigned through
+    C.pointer to graph stays referenced by this one."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("graph", C.POINTER(BeamLogpGraph)), ("normalized", C.c_int), ("max_active", C.c_int),
+                ("beam", C.c_float), ("logp", c_fp), ("status", c_fp), ("peak", c_fp), ("workspace", c_fp)]
+
+
+class CtcGraphBeamLogpGradArgs(C.Structure):
+    """oe_ctc_graph_beam_logp_grad_args (include/openeat_hip.h); filled by ops.ctc_graph_beam_logp's backward."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("graph", C.POINTER(BeamLogpGraph)), ("normalized", C.c_int), ("max_active", C.c_int),
+                ("beam", C.c_float), ("g", c_fp), ("dlogits", c_fp), ("logp", c_fp), ("status", c_fp), ("peak", c_fp),
+                ("workspace", c_fp)]
+
+
 class GraphSet(C.Structure):
     """oe_graph_set (include/openeat_hip.h); filled by graph_set."""
     _fields_ = [("G", C.c_int), ("Q", C.c_int), ("A", C.c_int), ("U", C.c_int), ("Qmax", C.c_int), ("Amax", C.c_int), ("n_inv", C.c_int),
@@ -360,6 +383,10 @@ _SIGNATURES = {
     "oe_ctc_graph_logp_grad_workspace_bytes": (SZ, [I, I, I, I, I]),
     "oe_ctc_graph_logp": (I, [C.POINTER(CtcGraphLogpArgs), P]),
     "oe_ctc_graph_logp_grad": (I, [C.POINTER(CtcGraphLogpGradArgs), P]),
+    "oe_ctc_graph_beam_logp_workspace_bytes": (SZ, [I, I, I, I, I, I]),
+    "oe_ctc_graph_beam_logp_grad_workspace_bytes": (SZ, [I, I, I, I, I, I]),
+    "oe_ctc_graph_beam_logp": (I, [C.POINTER(CtcGraphBeamLogpArgs), P]),
+    "oe_ctc_graph_beam_logp_grad": (I, [C.POINTER(CtcGraphBeamLogpGradArgs), P]),
     "oe_attention_fwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_attention_bwd": (I, [C.POINTER(AttnArgs), P]),
     "oe_relpos_prepare": (I, [P, L, L, P, L, P, P, I, I, I, I, F, P, P, P]),
@@ -716,6 +743,20 @@ def beam_graph(graph, device) -> BeamGraph:
     q = BeamGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
                   col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]), out_ptr.data_ptr(),
                   out_arc.data_ptr())
+    q.owner = graph                                                # the pointers live as long as the struct
+    return q
+
+
+def beam_logp_graph(graph, device) -> BeamLogpGraph:
+    """The oe_beam_logp_graph of `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph of either size: oe_beam_graph's
+    tables and the per-arc label-group tables on `device` (the graph keeps them, the struct keeps the graph)."""
+    in_ptr, src, dst, label, col, w, final, cols = graph.device_tables(device)
+    out_ptr, out_arc = graph.device_out_tables(device)
+    in_grp, in_xg, out_grp, out_xg, inv = graph.device_group_tables(device)
+    q = BeamLogpGraph(int(final.shape[0]), int(src.shape[0]), in_ptr.data_ptr(), src.data_ptr(), dst.data_ptr(), label.data_ptr(),
+                      col.data_ptr(), w.data_ptr(), final.data_ptr(), cols.data_ptr(), int(cols.shape[0]), out_ptr.data_ptr(),
+                      out_arc.data_ptr(), in_grp.data_ptr(), in_xg.data_ptr(), out_grp.data_ptr(), out_xg.data_ptr(), inv.data_ptr(),
+                      int(inv.shape[0]))
     q.owner = graph                                                # the pointers live as long as the struct
     return q
 

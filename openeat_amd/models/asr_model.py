@@ -209,7 +209,8 @@ class ASRModel(torch.nn.Module):
                           logp=logp.detach(), errors=errors, prefixes=prefixes, plen=plen)
 
     def ctc_graph_loss(self, features: torch.Tensor, features_length: torch.Tensor, graphs, graph_of=None,
-                       targets: Optional[torch.Tensor] = None, targets_length: Optional[torch.Tensor] = None):
+                       targets: Optional[torch.Tensor] = None, targets_length: Optional[torch.Tensor] = None,
+                       denominator=None, den_beam: float = 12.0, den_scale: float = 1.0, den_max_active: Optional[int] = None):
         """Training against decoding graphs (what k2 / WeNet users know as a graph CTC loss; the reference trains on one
         spelling only): `graphs` a DecodingGraph, a list of them or a GraphSet (openeat_amd.utils.decoding_graph; transcripts
         with alternatives come from DecodingGraph.from_alternatives), graph_of (B) the graph of each utterance (None: graph 0
@@ -217,6 +218,11 @@ class ASRModel(torch.nn.Module):
         oe_ctc_graph_logp), and loss_ctc = -(the sum of logp over the feasible utterances) / B, the zero_infinity convention
         of the CTC head.  With `targets` (the canonical spelling) and ctc_weight < 1 the attention losses are computed on
         them and combined as in forward(); otherwise the result is the CTC term alone.  Eager only; no host read.
+        denominator (a DecodingGraph of any size; MMI-style training): logp_den = ops.ctc_graph_beam_logp over that one graph
+        with beam den_beam and max_active den_max_active (default 16384; semantics at oe_ctc_graph_beam_logp), and loss_ctc =
+        -(the sum over the feasible utterances of logp - den_scale * logp_den) / B, feasible meaning both terms are finite.
+        This path reads the denominator's status and peak on the host, one D2H copy per round, to run overflowed utterances
+        again with max_active doubled (one copy when nothing overflows); `info` gains logp_den.
         -> loss, info: device tensors logp (B), feasible (B) bool, acc (None without the attention term)."""
         assert features.shape[0] == features_length.shape[0]
         ops.predrop_clear()
@@ -225,14 +231,25 @@ class ASRModel(torch.nn.Module):
         logits = self.ctc.logits(encoder_out)
         logp = ops.ctc_graph_logp(logits, encoder_out_lens, graphs, graph_of)
         feasible = torch.isfinite(logp.detach())
-        loss_ctc = -torch.where(feasible, logp, torch.zeros_like(logp)).sum() / logp.shape[0]
+        logp_den = None
+        if denominator is not None:
+            logp_den = self._graph_beam_logp(logits, encoder_out_lens, denominator, float(den_beam),
+                                             16384 if den_max_active is None else int(den_max_active), 1 << 30)[0]
+            feasible = feasible & torch.isfinite(logp_den.detach())
+            term = logp - float(den_scale) * logp_den
+        else:
+            term = logp
+        loss_ctc = -torch.where(feasible, term, torch.zeros_like(logp)).sum() / logp.shape[0]
         acc = None
         loss = loss_ctc
         if targets is not None and self.ctc_weight < 1:
             assert targets_length is not None and targets.shape[0] == targets_length.shape[0] == features.shape[0]
             l_loss, r_loss, acc = self._att_losses(encoder_out, encoder_mask, targets, targets_length)
             loss = self._joint_loss(loss_ctc, l_loss, r_loss)
-        return loss, dict(logp=logp.detach(), feasible=feasible, acc=acc)
+        info = dict(logp=logp.detach(), feasible=feasible, acc=acc)
+        if logp_den is not None:
+            info["logp_den"] = logp_den.detach()
+        return loss, info
 
     @torch.no_grad()
     def ctc_nbest(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int):
@@ -503,7 +520,7 @@ class ASRModel(torch.nn.Module):
     def ctc_graph_search(self, features: torch.Tensor, features_length: torch.Tensor, graph, window: Optional[int] = None,
                          margin: int = 16, with_times: bool = False, frame_shift_ms: float = 10, posterior: bool = False,
                          beam: Optional[float] = None, max_active: Optional[int] = None, workspace_cap: int = 1 << 30,
-                         nbest: Optional[int] = None, distinct: str = "arcs"):
+                         nbest: Optional[int] = None, distinct: str = "arcs", posterior_beam: Optional[float] = None):
         """Grammar-constrained CTC decoding (the reference has none; semantics in include/openeat_hip.h, oe_ctc_graph): the
         best path of each utterance through `graph`, an openeat_amd.utils.decoding_graph.DecodingGraph - the output is in the
         grammar by construction, or the utterance is infeasible.  Logits by ctc_logits_windowed (window None: one plain pass),
@@ -512,6 +529,9 @@ class ASRModel(torch.nn.Module):
         posterior=True: each result also carries log_mass, the graph's total log-likelihood on the normalised posteriors
         (ops.ctc_graph_logp: with zero weights log P(the labelling is in the grammar), a rejection score), and posterior =
         exp(score - log_mass), the best path's share of it; one more recursion on the device and one more D2H copy.
+        posterior_beam a float >= 0 or inf (with or without posterior=True, with either search): log_mass and posterior come
+        from the beam-pruned sum instead (ops.ctc_graph_beam_logp with that beam; semantics at oe_ctc_graph_beam_logp), which
+        takes a graph of any size; an utterance that overflows max_active is run again with it doubled, as the beam search's.
         beam None: the dense search (oe_ctc_graph; graphs of at most 8064 nodes and 16384 arcs).  beam a float >= 0 or inf:
         the token-passing search (oe_ctc_graph_beam), the one a large=True graph has: after every frame but the last the
         states below the frame's best - beam are dropped, and max_active (default 16384) is how many survivors a frame can
@@ -524,9 +544,10 @@ class ASRModel(torch.nn.Module):
         from openeat_amd.utils.decoding_graph import LOGP_MAX_ARCS, LOGP_MAX_NODES, DecodingGraph, graph_results
         if not isinstance(graph, DecodingGraph):
             raise ValueError(f"graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
-        if posterior and (graph.num_nodes > LOGP_MAX_NODES or graph.num_arcs > LOGP_MAX_ARCS):
+        if posterior and posterior_beam is None and (graph.num_nodes > LOGP_MAX_NODES or graph.num_arcs > LOGP_MAX_ARCS):
             raise ValueError(f"posterior=True needs the graph's total likelihood (oe_ctc_graph_logp), which takes at most {LOGP_MAX_NODES} "
-                             f"nodes and {LOGP_MAX_ARCS} arcs; this graph has {graph.num_nodes} / {graph.num_arcs}")
+                             f"nodes and {LOGP_MAX_ARCS} arcs; this graph has {graph.num_nodes} / {graph.num_arcs} (posterior_beam gives "
+                             "the beam-pruned sum, which takes it)")
         if beam is None and max_active is not None:
             raise ValueError("max_active belongs to the beam search: give a beam (inf for none) with it")
         if nbest is not None and beam is not None:
@@ -546,8 +567,12 @@ class ASRModel(torch.nn.Module):
         times = (lambda t0, t1: frame_times(t0, t1, rate, frame_shift_ms)) if with_times else None
         results = graph_results(graph, sc.tolist(), n.tolist(), a.view(B, M).tolist(), s.view(B, M).tolist(), e.view(B, M).tolist(),
                                 lg.view(B, M).tolist(), times)
-        if posterior:
-            mass = ops.ctc_graph_logp(logits, lens, graph).cpu().tolist()
+        if posterior or posterior_beam is not None:
+            if posterior_beam is None:
+                mass = ops.ctc_graph_logp(logits, lens, graph).cpu().tolist()
+            else:
+                mass = self._graph_beam_logp(logits, lens, graph, float(posterior_beam), 16384 if max_active is None else int(max_active),
+                                             int(workspace_cap))[0].cpu().tolist()
             for res, m, best in zip(results, mass, score.cpu().tolist()):
                 if res.feasible:
                     res.log_mass, res.posterior = m, min(math.exp(best - m), 1.0)
@@ -628,6 +653,30 @@ class ASRModel(torch.nn.Module):
             part = ops.ctc_graph_beam_decode(logits[idx], lens[idx], graph, beam, max_active, workspace_cap=workspace_cap)
             for whole, redone in zip(outs, part):
                 whole[idx] = redone
+
+    @staticmethod
+    def _graph_beam_logp(logits, lens, graph, beam, max_active, workspace_cap):
+        """ops.ctc_graph_beam_logp with _graph_beam_decode's retry, differentiable: the utterances that overflowed run again
+        with max_active doubled (and at least their peak), while one utterance's gradient workspace fits workspace_cap.  One D2H
+        copy of status and peak per round.  -> (logp, status, peak)."""
+        B, T, _ = logits.shape
+        logp, status, peak = ops.ctc_graph_beam_logp(logits, lens, graph, beam, max_active, workspace_cap=workspace_cap)
+        while True:
+            st, pk = torch.stack([status, peak]).cpu().tolist()
+            over = [b for b in range(B) if st[b] == hip.CTC_GRAPH_BEAM_OVERFLOW]
+            if not over:
+                return logp, status, peak
+            max_active = min(max(2 * max_active, max(pk[b] for b in over)), graph.num_nodes + graph.num_arcs)   # Q + A never overflows
+            need = hip.lib().oe_ctc_graph_beam_logp_grad_workspace_bytes(1, T, len(graph.cols), graph.num_nodes, graph.num_arcs, max_active)
+            if need > workspace_cap:
+                b = max(over, key=lambda i: pk[i])
+                raise RuntimeError(f"ctc_graph_beam_logp: utterance {b} keeps {pk[b]} states alive in one frame (peak), and max_active="
+                                   f"{max_active} needs {need} bytes of workspace for one utterance, over workspace_cap={workspace_cap}: "
+                                   "narrow the beam or raise the cap")
+            idx = torch.tensor(over, device=logits.device)
+            part = ops.ctc_graph_beam_logp(logits[idx], lens[idx], graph, beam, max_active, workspace_cap=workspace_cap)
+            logp = logp.index_copy(0, idx, part[0])
+            status, peak = status.index_copy(0, idx, part[1]), peak.index_copy(0, idx, part[2])
 
     @torch.no_grad()
     def ctc_topk_windowed(self, features: torch.Tensor, features_length: torch.Tensor, beam_size: int, window: Optional[int],

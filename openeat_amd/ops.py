@@ -2669,6 +2669,101 @@ def ctc_graph_logp(logits, hlens, graphs, graph_of=None, normalized=False, works
     return CTCGraphLogpFn.apply(logits, hl32, graphs, graph_of, bool(normalized), int(workspace_cap))
 
 
+class CTCGraphBeamLogpFn(torch.autograd.Function):
+    """oe_ctc_graph_beam_logp / oe_ctc_graph_beam_logp_grad (semantics in include/openeat_hip.h): the beam-pruned total
+    log-likelihood of a decoding graph of any size per utterance, differentiable with respect to raw logits.  The utterances
+    run in consecutive groups under the workspace cap, forward and backward, one workspace reused: exactly the results of one
+    call."""
+
+    @staticmethod
+    def _fill(a, buf, ld, hl32, g, lo, n, T, V, beam, max_active, normalized, ws):
+        a.logits, a.ldv, a.B, a.T, a.V = buf.data_ptr() + 4 * lo * T * ld, ld, n, T, V
+        a.hlens, a.graph, a.workspace = hl32[lo:].data_ptr(), hip.C.pointer(g), ws.data_ptr()
+        a.normalized, a.max_active, a.beam = int(bool(normalized)), max_active, beam
+
+    @staticmethod
+    def forward(ctx, logits, hl32, graph, beam, max_active, normalized, cap):
+        B, T, V = (int(s) for s in logits.shape)
+        # rows padded beyond V (CTCHeadFn's logits, a [..., :V] view of them) are taken as they are
+        if logits.stride(2) == 1 and logits.stride(1) >= V and logits.stride(0) == T * logits.stride(1) and logits.data_ptr() % 4 == 0:
+            buf, ld = logits, int(logits.stride(1))
+        else:
+            buf, ld = logits.contiguous(), V
+        dev = logits.device
+        lib = hip.lib()
+        U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
+        per_utt = lib.oe_ctc_graph_beam_logp_workspace_bytes(1, T, U, Q, A, max_active) if 1 <= max_active < 1 << 31 else 0
+        if per_utt == 0 or U >= V or not beam >= 0:
+            raise ValueError(f"ctc_graph_beam_logp: T={T} max_active={max_active} beam={beam} U={U} V={V} Q={Q} A={A} outside 1 <= T <= 2^20, "
+                             "1 <= max_active, 0 <= beam, 1 <= U < V, 1 <= Q <= 2^20, 1 <= A <= 2^22 (a graph without arcs has no device "
+                             "form)")
+        g = hip.beam_logp_graph(graph, dev)
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        peak = torch.empty(B, dtype=torch.int32, device=dev)
+        group = min(max(int(cap) // per_utt, 1), B)
+        ws = torch.empty(lib.oe_ctc_graph_beam_logp_workspace_bytes(group, T, U, Q, A, max_active), dtype=torch.uint8, device=dev)
+        for lo in range(0, B, group):
+            a = hip.CtcGraphBeamLogpArgs()
+            CTCGraphBeamLogpFn._fill(a, buf, ld, hl32, g, lo, min(group, B - lo), T, V, beam, max_active, normalized, ws)
+            a.logp, a.status, a.peak = logp[lo:].data_ptr(), status[lo:].data_ptr(), peak[lo:].data_ptr()
+            hip.check(lib.oe_ctc_graph_beam_logp(hip.C.byref(a), hip.stream()), "oe_ctc_graph_beam_logp")
+        if ctx.needs_input_grad[0]:
+            if normalized:
+                raise ValueError("ctc_graph_beam_logp: the gradient is with respect to raw logits (normalized=False)")
+            ctx.save_for_backward(buf, hl32)
+            ctx.cfg = (B, T, V, ld, graph, beam, max_active, int(cap))
+        ctx.mark_non_differentiable(status, peak)
+        return logp, status, peak
+
+    @staticmethod
+    def backward(ctx, g, _status, _peak):
+        buf, hl32 = ctx.saved_tensors
+        B, T, V, ld, graph, beam, max_active, cap = ctx.cfg
+        g = _chk(g, "ctc_graph_beam_logp gradient")
+        dev = buf.device
+        lib = hip.lib()
+        U, Q, A = len(graph.cols), graph.num_nodes, graph.num_arcs
+        per_utt = lib.oe_ctc_graph_beam_logp_grad_workspace_bytes(1, T, U, Q, A, max_active)
+        gr = hip.beam_logp_graph(graph, dev)
+        dlogits = torch.empty(B, T, ld, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        peak = torch.empty(B, dtype=torch.int32, device=dev)
+        group = min(max(cap // per_utt, 1), B)
+        ws = torch.empty(lib.oe_ctc_graph_beam_logp_grad_workspace_bytes(group, T, U, Q, A, max_active), dtype=torch.uint8, device=dev)
+        for lo in range(0, B, group):
+            a = hip.CtcGraphBeamLogpGradArgs()
+            CTCGraphBeamLogpFn._fill(a, buf, ld, hl32, gr, lo, min(group, B - lo), T, V, beam, max_active, False, ws)
+            a.g, a.dlogits, a.logp = g[lo:].data_ptr(), dlogits[lo].data_ptr(), None
+            a.status, a.peak = status[lo:].data_ptr(), peak[lo:].data_ptr()
+            hip.check(lib.oe_ctc_graph_beam_logp_grad(hip.C.byref(a), hip.stream()), "oe_ctc_graph_beam_logp_grad")
+        return dlogits[..., :V], None, None, None, None, None, None
+
+
+def ctc_graph_beam_logp(logits, hlens, graph, beam, max_active=16384, normalized=False, workspace_cap=1 << 30):
+    """The beam-pruned total log-likelihood of a decoding graph of any size (oe_ctc_graph_beam_logp; semantics in
+    include/openeat_hip.h): logits (B, T, V) float32 (raw, or log-probabilities with normalized=True), hlens (B), graph an
+    openeat_amd.utils.decoding_graph.DecodingGraph, beam >= 0 or inf, max_active the survivors a frame can record ->
+    (logp (B) float32, -inf for an infeasible or overflowed utterance; status (B) int32: 0 summed, 1 infeasible, 2 overflow;
+    peak (B) int32: the largest survivor count, on overflow the overflowing one).  logp is differentiable with respect to raw
+    logits, the survivor sets held fixed (an infeasible or overflowed utterance takes a zero gradient); padded-row views are
+    taken as CTCNbestFn takes them.  Where the workspace exceeds workspace_cap the utterances run in consecutive groups, one
+    workspace reused, forward and backward: exactly the results of one call.  No host read."""
+    from openeat_amd.utils.decoding_graph import DecodingGraph
+    if not isinstance(graph, DecodingGraph):
+        raise TypeError(f"ctc_graph_beam_logp: graph must be an openeat_amd.utils.decoding_graph.DecodingGraph (got {type(graph).__name__})")
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3):
+        raise TypeError("ctc_graph_beam_logp: logits must be a float32 (B, T, V) CUDA tensor; there is no CPU fallback")
+    pend = _PENDING_LNF.take(logits)
+    if pend is not None:
+        pend.resolve()
+    B = int(logits.shape[0])
+    if B < 1 or tuple(hlens.shape) != (B,):
+        raise ValueError(f"ctc_graph_beam_logp: B={B} utterances need hlens (B), got {tuple(hlens.shape)}")
+    hl32 = hlens.to(device=logits.device, dtype=torch.int32).contiguous()
+    return CTCGraphBeamLogpFn.apply(logits, hl32, graph, float(beam), int(max_active), bool(normalized), int(workspace_cap))
+
+
 def ngram_score(lm, tokens, lens, bos: bool = True, eos: bool = True, per_token: bool = False):
     """Back-off n-gram LM scores of R hypotheses (oe_ngram_score; asr_model.py:515-516 for all of them at once): `lm` an
     openeat_amd.models.ngram_lm.NgramLM, tokens (R, ld) integer token ids and lens (R) on the device (a negative length:

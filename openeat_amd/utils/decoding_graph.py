@@ -1,6 +1,7 @@
 """Host side of grammar-constrained CTC decoding (ASRModel.ctc_graph_search, ops.ctc_graph_decode, ops.ctc_graph_beam_decode,
 ops.ctc_graph_nbest; semantics in include/openeat_hip.h, oe_ctc_graph, oe_ctc_graph_beam and oe_ctc_graph_nbest): the token graph with the tables the kernels read, its
-builders, and the records made of the kernels' outputs; and GraphSet, the packed form oe_ctc_graph_logp reads.  No kernel here."""
+builders, and the records made of the kernels' outputs; GraphSet, the packed form oe_ctc_graph_logp reads; and the per-arc
+label-group tables oe_ctc_graph_beam_logp reads, for a graph of either size.  No kernel here."""
 import math
 from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence
@@ -93,6 +94,8 @@ class DecodingGraph:
         self.skipped = 0
         self._device: Dict[object, tuple] = {}
         self._device_out: Dict[object, tuple] = {}
+        self._groups: Optional[tuple] = None
+        self._device_groups: Dict[object, tuple] = {}
 
     @classmethod
     def from_arrays(cls, num_nodes: int, src, dst, label, w, final, outputs: Optional[Sequence] = None, large: bool = False) -> "DecodingGraph":
@@ -287,6 +290,31 @@ class DecodingGraph:
         """host_out_tables() on `device`; made once per device and kept."""
         return self._on_device(self._device_out, self.host_out_tables, device)
 
+    def host_group_tables(self):
+        """The label-group tables oe_beam_logp_graph adds to host_tables() and host_out_tables(), as numpy, made once and kept:
+        (in_grp, in_xg, out_grp, out_xg, inv).  The groups and their ids are _group_tables' (those of a GraphSet of this one
+        graph): in_grp[a] = the in-group of dst[a] that holds a, out_grp[a] = the out-group of src[a] that holds a; in_xg,
+        out_xg and inv as in oe_graph_set."""
+        if self._groups is None:
+            Q, A, U = self.num_nodes, self.num_arcs, len(self.cols)
+
+            def group_of(perm, gstart):
+                grp = np.empty(A, dtype=np.int32)
+                grp[perm] = np.searchsorted(gstart[:int(np.count_nonzero(gstart < A))], np.arange(A), side="right") - 1
+                return grp
+
+            in_perm, in_gstart, _, in_xg = _group_tables(self.dst, self.src, self.col, Q, U)
+            out_perm, out_gstart, _, out_xg = _group_tables(self.src, self.dst, self.col, Q, U)
+            inv = np.full((int(self.cols.max()) if U else 0) + 1, -1, dtype=np.int32)
+            inv[0] = 0
+            inv[self.cols] = 1 + np.arange(U, dtype=np.int32)
+            self._groups = (group_of(in_perm, in_gstart), in_xg, group_of(out_perm, out_gstart), out_xg, inv)
+        return tuple(a.copy() for a in self._groups)
+
+    def device_group_tables(self, device):
+        """host_group_tables() on `device`; made once per device and kept."""
+        return self._on_device(self._device_groups, self.host_group_tables, device)
+
     def accepts(self, frames: Sequence[int]) -> bool:
         """Does the graph accept the frame labelling `frames` (0 = blank) under the CTC topology?  A set simulation over the
         node and arc states of oe_ctc_graph, weights ignored."""
@@ -411,7 +439,8 @@ class GraphResult:
     it - and with times "start_s" / "end_s";  score: the path's value, weights and final weight included (-inf if infeasible);
     truncated: more traversals than were asked for, only the first are listed;  log_mass, posterior (ctc_graph_search with
     posterior=True, else None): the graph's total log-likelihood on the normalised posteriors (oe_ctc_graph_logp) - with zero
-    weights log P(the labelling is in the grammar) - and exp(score - log_mass), the best path's share of it;  nbest
+    weights log P(the labelling is in the grammar) - and exp(score - log_mass), the best path's share of it (with
+    posterior_beam: of the beam-pruned sum, oe_ctc_graph_beam_logp);  nbest
     (ctc_graph_search with nbest=K, else None): the K best distinct paths as GraphHypothesis, best first."""
     feasible: bool
     score: float
