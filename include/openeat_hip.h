@@ -1607,6 +1607,96 @@ int oe_ctc_nbest_grad(const float* logits, long ldv, int B, int T, int V, const 
                       const int* hyp_lens, int group, int Lmax, const float* logp, const float* g, const void* saved,
                       float* dlogits, void* workspace, void* stream);
 
+/* Transducer (RNN-T) loss on device: the log-likelihood of a label sequence under the transducer lattice (Graves 2012, the
+ * interface of warp-transducer) and its gradient with respect to the raw joint logits.  No counterpart in the reference, which
+ * has no transducer.  These are the semantics every layer refers to (ops.rnnt_loss; the yardstick is tests/rnnt_ref.py).
+ *   logits (B, T, Umax+1, ldv >= V) f32, raw.  hlens (B) i32 frames, ulens (B) i32 labels, targets (B, Umax) i32 (NULL allowed
+ *   when Umax = 0), all on the device.  For utterance b: Tb = hlens[b] held to 0..T, Ub = ulens[b], y_1..y_Ub = targets[b,:Ub],
+ *     lp(t,u,v) = logits[b,t,u,v] - logsumexp_v logits[b,t,u,:]
+ *     alpha(0,0) = 0;  alpha(t,u) = logaddexp(alpha(t-1,u) + lp(t-1,u,blank), alpha(t,u-1) + lp(t,u-1,y_u))
+ *     logp[b] = alpha(Tb-1,Ub) + lp(Tb-1,Ub,blank)
+ *     beta(Tb-1,Ub) = lp(Tb-1,Ub,blank);  beta(t,u) = logaddexp(beta(t+1,u) + lp(t,u,blank), beta(t,u+1) + lp(t,u,y_{u+1}))
+ *   Tb = 0 gives logp[b] = -inf exactly and a zero gradient (the zero-infinity convention of oe_ctc_loss_fused).  What only the
+ *   device can see is checked there, without a fault: ulens[b] outside 0..Umax, or a target within the length that is blank or
+ *   outside 0..V-1 (it is never used as an index), makes the utterance INFEASIBLE: status[b] = 1, logp[b] = -inf, a zero
+ *   gradient; status[b] = 0 otherwise.  status (B) i32 may be NULL.
+ * oe_rnnt_loss: the row pass and the lattice pass; writes logp (B) f32 and leaves in `workspace` what oe_rnnt_grad needs.
+ *   workspace: oe_rnnt_workspace_bytes(B,T,Umax) bytes, 16-byte aligned; with N = B*T*(Umax+1): the row log-sum-exp (4N,
+ *   [b][t][u]), lp of the blank and of the next label (4N each, [b][u][t]), alpha and beta (8N each, [b][u][t]), logZ in the
+ *   log2 domain (8B) and a status word per utterance (4B), each part rounded up to 16 bytes.
+ * oe_rnnt_grad: the same logits, ldv, shape, hlens, targets, ulens, blank and workspace as the oe_rnnt_loss call before it, the
+ *   logits unchanged since; g (B) f32.  At a node t < Tb, u <= Ub of a feasible utterance
+ *     e_b = exp(alpha(t,u) + lp(t,u,blank)   + beta(t+1,u) - logp)   (beta(Tb,Ub) := 0; absent for t = Tb-1, u < Ub)
+ *     e_y = exp(alpha(t,u) + lp(t,u,y_{u+1}) + beta(t,u+1) - logp)   (absent for u = Ub)
+ *     dlogits[b,t,u,v] = g[b] * ([v = blank] e_b + [v = y_{u+1}] e_y - (e_b + e_y) * softmax(t,u)[v])
+ *   the gradient of sum_b g[b] * logp[b].  The node's occupancy is the sum of its outgoing terms, never exp(alpha + beta - logp):
+ *   at a confident node the cancellation against softmax ~ 1 then carries no drift of the recursions.  Every other node of the
+ *   (B, T, Umax+1) grid is written as exact zeros; columns >= V are never written.  g of an infeasible utterance is not read into
+ *   any result (it may be NaN).  dlogits (B, T, Umax+1, ldv) MAY be the logits buffer itself (the convention of
+ *   oe_lsm_loss_fused): every element is read before it is written, by the same lane.
+ * Numbers: the row pass sums exp in float32 and keeps lp = (x - max) - log(sum); alpha and beta are float64 in the log2 domain
+ *   with the finite "log 0" of the CTC kernels, exp / log float32 on differences.  Against the float64 restatement: logp rtol
+ *   1e-4 / atol 1e-3, gradient rtol 2e-3 / atol 2e-5 * |g[b]|, the tolerances of oe_ctc_loss_fused; the measured fractions are
+ *   in DESIGN.md.
+ * Limits: 1 <= B, 1 <= T <= OE_RNNT_MAX_T, 0 <= Umax <= OE_RNNT_MAX_U, 2 <= V, ldv >= V, 0 <= blank < V, B*T*(Umax+1) < 2^31.
+ *   Anything else, a NULL required pointer (logits, hlens, ulens, targets when Umax > 0, logp / g, dlogits, workspace) and a
+ *   workspace not 16-byte aligned are reported through oe_last_error before any launch, with the outputs untouched.
+ *   oe_rnnt_workspace_bytes returns 0 outside the limits.
+ * Launches: row pass, one wave per node inside the lattice (nodes outside are not read); lattice pass, one workgroup of two
+ *   waves per utterance, alpha and beta side by side, a lane per label position (1, 2 or 4 positions per lane), a step per
+ *   anti-diagonal, the label predecessor by one DPP shift, lp fetched a chunk of steps ahead; gradient pass, one wave per node.
+ *   No float atomics, every sum in a fixed order: outputs are bit-identical from run to run.  No allocation, no host read, no
+ *   host-side state: capturable. */
+#define OE_RNNT_MAX_T 8192
+#define OE_RNNT_MAX_U 255
+typedef struct oe_rnnt_args {
+    const float* logits; long ldv; int B, T, Umax, V;
+    const int* hlens;
+    const int* targets;   /* (B, Umax) */
+    const int* ulens;
+    int blank;
+    float* logp;          /* (B) */
+    int* status;          /* (B) or NULL */
+    void* workspace;
+} oe_rnnt_args;
+typedef struct oe_rnnt_grad_args {
+    const float* logits; long ldv; int B, T, Umax, V;
+    const int* hlens;
+    const int* targets;
+    const int* ulens;
+    int blank;
+    const float* g;       /* (B) */
+    float* dlogits;       /* (B, T, Umax+1, ldv); may be logits */
+    void* workspace;      /* as oe_rnnt_loss left it */
+} oe_rnnt_grad_args;
+size_t oe_rnnt_workspace_bytes(int B, int T, int Umax);
+int oe_rnnt_loss(const oe_rnnt_args* args, void* stream);
+int oe_rnnt_grad(const oe_rnnt_grad_args* args, void* stream);
+
+/* The joint network's broadcast: z[b,t,u,:] = act(e[b,t,:] + p[b,u,:]) for e (B, T, J) and p (B, U1, J), U1 = Umax + 1, act one
+ * of the activation codes (0 none, 1 relu, 2 swish, 3 tanh, 4 hardtanh, 5 selu, 6 gelu).  No counterpart in the reference.
+ *   hlens, ulens (B) i32 or NULL (NULL: every frame / every position).  A node is inside the lattice when t < hlens[b] and
+ *   u <= ulens[b].  The forward writes EVERY node of z (B, T, U1, J): zeros outside the lattice, because the projection behind it
+ *   reads them all.  The backward recomputes the pre-activation from e and p (nothing is stored):
+ *     de[b,t,:] = sum over u of dz[b,t,u,:] * act'(e[b,t,:] + p[b,u,:])   one workgroup per (b,t), u ascending
+ *     dp[b,u,:] = sum over t of dz[b,t,u,:] * act'(e[b,t,:] + p[b,u,:])   one workgroup per (b,u), t ascending
+ *   over the nodes inside the lattice only; rows (b,t) and (b,u) with no such node are zeros.  The order of every sum is fixed:
+ *   bit-identical from run to run.  Limits: 1 <= B, T, U1, J and B*T*U1 < 2^31; NULL e, p, z (dz, de, dp) and an unknown act are
+ *   reported before any launch.  One launch each, no workspace, no atomics: capturable. */
+typedef struct oe_joint_combine_args {
+    const float* e; const float* p; int B, T, U1, J, act;
+    const int* hlens; const int* ulens;
+    float* z;
+} oe_joint_combine_args;
+typedef struct oe_joint_combine_bwd_args {
+    const float* e; const float* p; int B, T, U1, J, act;
+    const int* hlens; const int* ulens;
+    const float* dz;
+    float* de; float* dp;
+} oe_joint_combine_bwd_args;
+int oe_joint_combine_fwd(const oe_joint_combine_args* args, void* stream);
+int oe_joint_combine_bwd(const oe_joint_combine_bwd_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

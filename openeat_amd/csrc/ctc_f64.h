@@ -24,6 +24,11 @@ __device__ __forceinline__ double nb_lse3_add(double a, double b, double c, floa
     const float s = nb_exp2((float)(a - m)) + nb_exp2((float)(b - m)) + nb_exp2((float)(c - m));
     return (m + (double)add) + (double)nb_log2(s);
 }
+// log2(2^a + 2^b) + add: the two-term form (the transducer lattice, rnnt.hip)
+__device__ __forceinline__ double nb_lse2_add(double a, double b, double add) {
+    const double m = fmax(a, b);
+    return (m + add) + (double)nb_log2(1.f + nb_exp2((float)(fmin(a, b) - m)));
+}
 
 template <bool FWD, int NS, int CH, bool FULL>
 __device__ __forceinline__ void nb_chunk(int c0, int Tb, const long (&ostr)[NS], double (&a)[NS], const double (&cap)[NS],

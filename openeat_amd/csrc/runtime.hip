@@ -14,7 +14,7 @@ extern "C" void oe_set_error(const char* fmt, ...) {
 
 extern "C" const char* oe_last_error(void) { return g_err; }
 
-extern "C" int oe_abi_version(void) { return 9; }
+extern "C" int oe_abi_version(void) { return 10; }
 
 // ---- capture hygiene ------------------------------------------------------------------------------------------------
 // A stream capture that forks work onto other streams must lead every fork back into the origin stream before

@@ -325,6 +325,32 @@ class CtcGraphLogpGradArgs(C.Structure):
                 ("g", c_fp), ("dlogits", c_fp), ("logp", c_fp), ("workspace", c_fp)]
 
 
+class RnntArgs(C.Structure):
+    """oe_rnnt_args (include/openeat_hip.h); filled by ops.rnnt_loss."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("Umax", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("targets", c_fp), ("ulens", c_fp), ("blank", C.c_int), ("logp", c_fp), ("status", c_fp),
+                ("workspace", c_fp)]
+
+
+class RnntGradArgs(C.Structure):
+    """oe_rnnt_grad_args (include/openeat_hip.h); filled by ops.rnnt_loss's backward."""
+    _fields_ = [("logits", c_fp), ("ldv", C.c_long), ("B", C.c_int), ("T", C.c_int), ("Umax", C.c_int), ("V", C.c_int),
+                ("hlens", c_fp), ("targets", c_fp), ("ulens", c_fp), ("blank", C.c_int), ("g", c_fp), ("dlogits", c_fp),
+                ("workspace", c_fp)]
+
+
+class JointCombineArgs(C.Structure):
+    """oe_joint_combine_args (include/openeat_hip.h); filled by ops.joint_combine."""
+    _fields_ = [("e", c_fp), ("p", c_fp), ("B", C.c_int), ("T", C.c_int), ("U1", C.c_int), ("J", C.c_int), ("act", C.c_int),
+                ("hlens", c_fp), ("ulens", c_fp), ("z", c_fp)]
+
+
+class JointCombineBwdArgs(C.Structure):
+    """oe_joint_combine_bwd_args (include/openeat_hip.h); filled by ops.joint_combine's backward."""
+    _fields_ = [("e", c_fp), ("p", c_fp), ("B", C.c_int), ("T", C.c_int), ("U1", C.c_int), ("J", C.c_int), ("act", C.c_int),
+                ("hlens", c_fp), ("ulens", c_fp), ("dz", c_fp), ("de", c_fp), ("dp", c_fp)]
+
+
 I, L, F, D, P, U64, SZ =C.c_int, C.c_long, C.c_float, C.c_double, c_fp, C.c_ulonglong, C.c_size_t
 _SIGNATURES = {
     "oe_last_error": (C.c_char_p, []),
@@ -450,6 +476,11 @@ _SIGNATURES = {
     "oe_grad_norm_workspace_floats": (SZ, []),
     "oe_grad_norm": (I, [P, L, P, P, P]),
     "oe_adam_step": (I, [P, P, P, P, L, P, F, F, F, F, F, P, P, P]),
+    "oe_rnnt_workspace_bytes": (SZ, [I, I, I]),
+    "oe_rnnt_loss": (I, [C.POINTER(RnntArgs), P]),
+    "oe_rnnt_grad": (I, [C.POINTER(RnntGradArgs), P]),
+    "oe_joint_combine_fwd": (I, [C.POINTER(JointCombineArgs), P]),
+    "oe_joint_combine_bwd": (I, [C.POINTER(JointCombineBwdArgs), P]),
 }
 
 

@@ -208,6 +208,60 @@ class ASRModel(torch.nn.Module):
         return loss, dict(loss_mwer=loss_mwer.detach(), loss_base=base.detach(), acc=acc, expected_errors=expected.detach(),
                           logp=logp.detach(), errors=errors, prefixes=prefixes, plen=plen)
 
+    # ------------------------------------------------------------------ transducer --
+    def add_transducer(self, **head_conf):
+        """Give the model a transducer head over its encoder (modules/transducer.py; the reference has none): head_conf are
+        TransducerHead's keyword arguments (joint_dim, context_size, blank, activation, length_normalized_loss).  A model
+        without the head keeps exactly the state dict it had; with it the keys transducer.* are added."""
+        from openeat_amd.modules.transducer import TransducerHead
+        d_model = self.ctc.ctc_lo.in_features
+        self.transducer = TransducerHead(self.vocab_size, d_model, **head_conf).to(self.ctc.ctc_lo.weight.device)
+        return self.transducer
+
+    def _transducer_head(self, who):
+        head = getattr(self, "transducer", None)
+        if head is None:
+            raise RuntimeError(f"{who}: the model has no transducer head; call add_transducer() first")
+        return head
+
+    def forward_transducer(self, features: torch.Tensor, features_length: torch.Tensor, targets: torch.Tensor,
+                           targets_length: torch.Tensor, rnnt_weight: float = 1.0, base_weight: float = 0.0):
+        """Transducer training step: one encoder pass, then
+            loss = rnnt_weight * (the head's loss, -sum_b logp[b] / B) + base_weight * (the joint CTC/attention loss of forward()).
+        The base loss is not computed with base_weight == 0.  Eager only; no host read.
+        -> loss, info: device tensors logp (B), loss_rnnt, loss_base (None with base_weight == 0), acc (None unless the
+        attention decoder ran)."""
+        head = self._transducer_head("forward_transducer")
+        assert targets_length.dim() == 1, targets_length.shape
+        assert (features.shape[0] == features_length.shape[0] == targets.shape[0] == targets_length.shape[0]), \
+            (features.shape, features_length.shape, targets.shape, targets_length.shape)
+        ops.predrop_clear()
+        encoder_out, encoder_mask, _ = self._encode(features, features_length)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        logp = head.logp(encoder_out, encoder_out_lens, targets, targets_length)
+        loss_rnnt = head.loss_from_logp(logp, targets_length)
+        loss, base, acc = rnnt_weight * loss_rnnt, None, None
+        if base_weight != 0:
+            loss_ctc = self.ctc(encoder_out, encoder_out_lens, targets, targets_length)
+            if self.ctc_weight < 1:
+                l_loss, r_loss, acc = self._att_losses(encoder_out, encoder_mask, targets, targets_length)
+                base = self._joint_loss(loss_ctc, l_loss, r_loss)
+            else:
+                base = loss_ctc
+            loss = loss + base_weight * base
+        return loss, dict(logp=logp.detach(), loss_rnnt=loss_rnnt.detach(), loss_base=None if base is None else base.detach(), acc=acc)
+
+    def transducer_greedy_search(self, features: torch.Tensor, features_length: torch.Tensor,
+                                 max_symbols_per_frame: int = 3) -> List[List[int]]:
+        """Greedy transducer decoding (TransducerHead.greedy_search) -> the token list of each utterance.  The search runs on
+        the device; the tokens come to the host once, at the end."""
+        head = self._transducer_head("transducer_greedy_search")
+        with torch.no_grad():
+            encoder_out, encoder_mask, _ = self._encode(features, features_length)
+            tokens, lens, _ = head.greedy_search(encoder_out, encoder_mask.squeeze(1).sum(1), max_symbols_per_frame)
+        tokens, lens = tokens.cpu().tolist(), lens.cpu().tolist()
+        return [row[:n] for row, n in zip(tokens, lens)]
+
     def ctc_graph_loss(self, features: torch.Tensor, features_length: torch.Tensor, graphs, graph_of=None,
                        targets: Optional[torch.Tensor] = None, targets_length: Optional[torch.Tensor] = None,
                        denominator=None, den_beam: float = 12.0, den_scale: float = 1.0, den_max_active: Optional[int] = None):

@@ -2951,6 +2951,133 @@ def ctc_nbest_logp(logits, hlens, hyps, hyp_lens, group: int):
     return CTCNbestFn.apply(logits, hlens, hyps, hyp_lens, group)
 
 
+class RNNTLossFn(torch.autograd.Function):
+    """oe_rnnt_loss / oe_rnnt_grad (semantics in include/openeat_hip.h): the transducer log-likelihood per utterance,
+    differentiable with respect to the raw joint logits.  Forward: the row pass and the lattice pass; backward: the gradient
+    pass over the workspace the forward left - into the logits' own storage when inplace."""
+
+    @staticmethod
+    def forward(ctx, logits, hl32, tg32, ul32, blank, inplace):
+        B, T, U1, V = (int(s) for s in logits.shape)
+        # rows padded beyond V (a [..., :V] view of them) are taken as they are
+        ld = int(logits.stride(2))
+        if logits.stride(3) == 1 and ld >= V and logits.stride(1) == U1 * ld and logits.stride(0) == T * U1 * ld and logits.data_ptr() % 4 == 0:
+            buf = logits
+        else:
+            buf, ld = logits.contiguous(), V
+        lib = hip.lib()
+        nbytes = lib.oe_rnnt_workspace_bytes(B, T, U1 - 1)
+        if nbytes == 0:
+            raise ValueError(f"rnnt_loss: B={B} T={T} U+1={U1} outside 1 <= B, 1 <= T <= 8192, 1 <= U+1 <= 256, B*T*(U+1) < 2^31")
+        dev = logits.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        a = hip.RnntArgs()
+        a.logits, a.ldv, a.B, a.T, a.Umax, a.V = buf.data_ptr(), ld, B, T, U1 - 1, V
+        a.hlens, a.targets, a.ulens = hl32.data_ptr(), (tg32.data_ptr() if U1 > 1 else None), ul32.data_ptr()
+        a.blank, a.logp, a.status, a.workspace = int(blank), logp.data_ptr(), None, ws.data_ptr()
+        hip.check(lib.oe_rnnt_loss(hip.C.byref(a), hip.stream()), "oe_rnnt_loss")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(buf, hl32, tg32, ul32, ws)
+            ctx.cfg = (B, T, U1, V, ld, int(blank), bool(inplace))
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        buf, hl32, tg32, ul32, ws = ctx.saved_tensors
+        B, T, U1, V, ld, blank, inplace = ctx.cfg
+        g = _chk(g, "rnnt_loss gradient")
+        dl = buf if inplace else torch.empty_strided(buf.shape, buf.stride(), dtype=torch.float32, device=buf.device)
+        a = hip.RnntGradArgs()
+        a.logits, a.ldv, a.B, a.T, a.Umax, a.V = buf.data_ptr(), ld, B, T, U1 - 1, V
+        a.hlens, a.targets, a.ulens = hl32.data_ptr(), (tg32.data_ptr() if U1 > 1 else None), ul32.data_ptr()
+        a.blank, a.g, a.dlogits, a.workspace = blank, g.data_ptr(), dl.data_ptr(), ws.data_ptr()
+        hip.check(hip.lib().oe_rnnt_grad(hip.C.byref(a), hip.stream()), "oe_rnnt_grad")
+        if inplace:
+            torch.autograd.graph.increment_version(buf)      # the logits are gone: whoever saved them for a backward is told so
+        return dl, None, None, None, None, None
+
+
+def rnnt_loss(logits, hlens, targets, ulens, blank: int = 0, inplace: bool = False):
+    """The transducer (RNN-T) log-likelihood (oe_rnnt_loss; semantics in include/openeat_hip.h): logits (B, T, U+1, V) float32,
+    raw joint outputs; hlens (B) frames, targets (B, U) labels, ulens (B) label counts, int64 or int32 on the device -> logp (B)
+    float32.  hlens[b] <= 0, ulens[b] outside 0..U, and a target within the length that is blank or outside 0..V-1 give -inf and
+    a zero gradient.  Differentiable with respect to the logits (one launch in backward).  inplace=True writes that gradient
+    over the logits' own storage - the largest tensor of a transducer step is then held once, not twice: the logits CANNOT be
+    used after backward (their version counter is bumped, so autograd refuses a stale use), and backward runs once.  Padded-row
+    views ([..., :V] of wider rows) are taken as they are.  No host read: capturable."""
+    ts = (logits, hlens, targets, ulens)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise TypeError("rnnt_loss: openeat_amd ops need CUDA tensors; there is no CPU fallback")
+    if logits.dtype != torch.float32 or logits.dim() != 4:
+        raise TypeError(f"rnnt_loss: logits must be a float32 (B, T, U+1, V) tensor (got {logits.dtype}, {tuple(logits.shape)})")
+    B, T, U1, V = (int(s) for s in logits.shape)
+    if any(t.dtype.is_floating_point or t.dtype == torch.bool for t in ts[1:]) or hlens.shape != (B,) or ulens.shape != (B,) \
+            or tuple(targets.shape) != (B, U1 - 1):
+        raise TypeError(f"rnnt_loss: hlens (B), targets (B, U) and ulens (B) must be integer tensors with U + 1 = {U1} "
+                        f"(got {tuple(hlens.shape)}, {tuple(targets.shape)}, {tuple(ulens.shape)})")
+    if not (B >= 1 and T >= 1 and U1 >= 1 and V >= 2 and 0 <= int(blank) < V):
+        raise ValueError(f"rnnt_loss: B={B} T={T} U+1={U1} V={V} blank={blank}")
+    pend = _PENDING_LNF.take(logits)
+    if pend is not None:
+        pend.resolve()
+    return RNNTLossFn.apply(logits, hlens.to(torch.int32).contiguous(), targets.to(torch.int32).contiguous(),
+                            ulens.to(torch.int32).contiguous(), int(blank), bool(inplace))
+
+
+class JointCombineFn(torch.autograd.Function):
+    """oe_joint_combine_fwd / _bwd: z[b,t,u,:] = act(e[b,t,:] + p[b,u,:]), zeros outside each utterance's lattice; the backward
+    recomputes the pre-activation and sums over u (de) and over t (dp) in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, e, p, hl32, ul32, act):
+        e, p = _chk(e, "joint_combine"), _chk(p, "joint_combine")
+        B, T, J = (int(s) for s in e.shape)
+        U1 = int(p.shape[1])
+        z = torch.empty(B, T, U1, J, dtype=torch.float32, device=e.device)
+        a = hip.JointCombineArgs()
+        a.e, a.p, a.B, a.T, a.U1, a.J, a.act = e.data_ptr(), p.data_ptr(), B, T, U1, J, int(act)
+        a.hlens, a.ulens, a.z = hip.ptr(hl32), hip.ptr(ul32), z.data_ptr()
+        hip.check(hip.lib().oe_joint_combine_fwd(hip.C.byref(a), hip.stream()), "oe_joint_combine_fwd")
+        ctx.save_for_backward(e, p, *(t for t in (hl32, ul32) if t is not None))
+        ctx.cfg = (B, T, U1, J, int(act), hl32 is not None, ul32 is not None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        e, p, *rest = ctx.saved_tensors
+        B, T, U1, J, act, has_h, has_u = ctx.cfg
+        hl32 = rest.pop(0) if has_h else None
+        ul32 = rest.pop(0) if has_u else None
+        dz = _chk(dz, "joint_combine gradient")
+        de, dp = torch.empty_like(e), torch.empty_like(p)
+        a = hip.JointCombineBwdArgs()
+        a.e, a.p, a.B, a.T, a.U1, a.J, a.act = e.data_ptr(), p.data_ptr(), B, T, U1, J, act
+        a.hlens, a.ulens, a.dz, a.de, a.dp = hip.ptr(hl32), hip.ptr(ul32), dz.data_ptr(), de.data_ptr(), dp.data_ptr()
+        hip.check(hip.lib().oe_joint_combine_bwd(hip.C.byref(a), hip.stream()), "oe_joint_combine_bwd")
+        return de, dp, None, None, None
+
+
+def joint_combine(e, p, hlens=None, ulens=None, act=ACT_TANH):
+    """The joint network's broadcast (oe_joint_combine_fwd): e (B, T, J) encoder side, p (B, U+1, J) predictor side ->
+    z (B, T, U+1, J) = act(e[:, :, None] + p[:, None]); with hlens / ulens (B, integer, on the device) the nodes t >= hlens[b] or
+    u > ulens[b] are zeros and take no gradient.  act: an ACT_* code or its name.  Differentiable in e and p."""
+    if isinstance(act, str) or act is None:
+        act = ACT_IDS[act or "none"]
+    if not (isinstance(e, torch.Tensor) and isinstance(p, torch.Tensor) and e.dim() == 3 and p.dim() == 3 and e.shape[0] == p.shape[0]
+            and e.shape[2] == p.shape[2]):
+        raise TypeError("joint_combine: e (B, T, J) and p (B, U+1, J) must agree in B and J")
+    B = int(e.shape[0])
+    lens = []
+    for name, t in (("hlens", hlens), ("ulens", ulens)):
+        if t is not None:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and not t.dtype.is_floating_point and tuple(t.shape) == (B,)):
+                raise TypeError(f"joint_combine: {name} must be an integer (B,) CUDA tensor")
+            t = t.to(torch.int32).contiguous()
+        lens.append(t)
+    return JointCombineFn.apply(e, p, lens[0], lens[1], int(act))
+
+
 def _prefix_score_logp(name, logp, lens, group):
     if not (isinstance(logp, torch.Tensor) and logp.is_cuda) or not (lens is None or (isinstance(lens, torch.Tensor) and lens.is_cuda)):
         raise TypeError(f"{name}: openeat_amd ops need CUDA tensors; there is no CPU fallback")

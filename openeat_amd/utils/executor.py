@@ -22,6 +22,7 @@ class Executor:
         accum_grad = args.get("accum_grad", 1)
         reducer = args.get("grad_reducer", None)          # openeat_amd.ddp.GradAllReduce for data parallel runs
         mwer = args.get("mwer")                           # a dict of ASRModel.forward_mwer keyword arguments, or absent
+        transducer = args.get("transducer")               # a dict of ASRModel.forward_transducer keyword arguments, or absent
         fused = isinstance(optimizer, FusedAdam)
         if fused:
             optimizer.max_grad_norm = clip
@@ -58,6 +59,10 @@ class Executor:
                 # minimum word error rate training over the model's own n-best lists (ASRModel.forward_mwer)
                 loss, info = model.forward_mwer(**batch, **mwer)
                 acc = info["acc"]
+            elif transducer is not None:
+                # transducer training with the model's TransducerHead (ASRModel.add_transducer / forward_transducer)
+                loss, info = model.forward_transducer(**batch, **transducer)
+                acc = info["acc"]
             else:
                 loss, acc = model(**batch)
             loss = torch.mean(loss) / accum_grad
@@ -88,6 +93,8 @@ class Executor:
                     msg += "Acc:{:.4f} AAcc:{:.4f} ".format(acc.item(), total_acc / max(num_seen_utts, 1))
                 if mwer is not None:
                     msg += "MWER:{:.4f} ExpErr:{:.4f} ".format(info["loss_mwer"].item(), info["expected_errors"].mean().item())
+                elif transducer is not None:
+                    msg += "RNNT:{:.4f} ".format(info["loss_rnnt"].item())
                 logger.info(msg + "lr:{:.8f} rank:{}".format(lr, local_rank))
         return total_loss / max(num_seen_utts, 1), total_acc / max(num_seen_utts, 1)
 
